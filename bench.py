@@ -13,6 +13,7 @@ down.  Gradients are all-reduced over RCCL (xGMI) every step.
 Launch (the reference: ``mpiexec -n N python ...``, README.md:12, ref.py:61-63):
 
     python bench.py --gpus N [--steps K] [--warmup W]     # spawns N ranks itself
+    python bench.py --gpus N --full                       # + the post-run measurements below
     python -m torch.distributed.run --nproc-per-node N bench.py --gpus N ...
 
 Without a launcher, ``--gpus N > 1`` starts N fresh rank processes (before anything touches
@@ -33,12 +34,21 @@ all-reduce is measured, not assumed.
 
 Rank 0 prints ONE JSON line.  The timed region is exactly K full training steps (forward,
 loss, backward, gradient all-reduce, optimizer update), bracketed by barrier + device sync on
-both sides; the reported time is the max over ranks.  AFTER the timed region (``--no_extras``
-skips it) the same ranks measure, each for min(K, 50) steps: the step with the gradient sync
-switched off (= the single-GPU step of the same shard: parallel efficiency, exposed comm), the
-step's collectives alone (bus GB/s, overlap %), and the step at a fixed global batch equal to
-the 1-GPU dataset (8192 rows for the proxy: strong scaling, the reference's own scaling mode,
-BASELINE.md:36-39).
+both sides; the reported time is the max over ranks.  A plain run stops there: set-up,
+warm-up, the K timed steps, the JSON line.  With ``--full``, AFTER the timed region
+(``--no_extras`` skips it again) the same ranks measure, each for min(K, 50) steps: the step
+with the gradient sync switched off (= the single-GPU step of the same shard: parallel
+efficiency, exposed comm), the step's collectives alone (bus GB/s, overlap %), and the step at
+a fixed global batch equal to the 1-GPU dataset (8192 rows for the proxy: strong scaling, the
+reference's own scaling mode, BASELINE.md:36-39).  Without ``--full`` those fields of the line
+are null.
+
+``--dump-outputs DIR`` writes what the timed steps left behind after the last one -- what a
+caller of the training step holds afterwards: the fp32 master parameters, the momentum, the
+bf16 shadow weights (as float32) and the last step's loss -- as ``DIR/<name>.npy``.  Data and
+initial weights are seeded, so two builds run with the same arguments can be compared array
+for array.  An array of more than DUMP_MAX_ELEMS elements is written as a fixed, seeded sample
+(the same positions every run).
 
 ``--device cpu`` runs the same job on the CPU/gloo path (BASELINE config 1 plumbing): the
 multi-rank logic of this script is tested that way without a GPU.
@@ -124,8 +134,15 @@ def parse(argv=None):
                    help="steps per candidate timing in --comm_mode tune (untimed region)")
     p.add_argument("--force_comm", action="store_true",
                    help="use the RCCL gradient path even with one rank (smoke-tests comm overlap)")
+    p.add_argument("--full", action="store_true",
+                   help="after the timed region also run the efficiency / overlap / "
+                        "strong-scaling measurements (a plain run only times the steps)")
     p.add_argument("--no_extras", action="store_true",
-                   help="skip the post-timed-region efficiency / overlap / strong-scaling runs")
+                   help="with --full: skip the post-timed-region efficiency / overlap / "
+                        "strong-scaling runs after all")
+    p.add_argument("--dump-outputs", dest="dump_outputs", default=None, metavar="DIR",
+                   help="write the parameters, momentum, shadow weights and loss the last timed "
+                        "step left as DIR/<name>.npy (rank 0)")
     p.add_argument("--shared_gpu_rehearsal", action="store_true",
                    help="TESTING ONLY: let the N ranks share the visible GPU(s) (each rank its own "
                         "NCCL_HOSTID, RCCL over loopback) to rehearse the multi-rank code path on "
@@ -641,6 +658,9 @@ def run(a, job):
     # the fp32 master, the momentum and the bf16 shadow on every rank, all-gathered over gloo
     digests = pg.allgather_object(replica_digest(eng, gpu))
     replicas_equal = len(set(digests)) == 1
+    if a.dump_outputs and rank == 0:
+        # (after the digest: a sharded optimizer has re-assembled the full master and momentum)
+        dump_outputs(a.dump_outputs, eng, loss)
 
     # ---------------- after the timed region: what the BASELINE metric derives from it ----------
     extras = {}
@@ -808,7 +828,7 @@ def run(a, job):
     if rank == 0 and supervised():
         # the measurement so far, in case the extras never come back (the supervisor prints it)
         write_result(dict(line(), extras_error="extras did not finish", complete=False))
-    if not a.no_extras:
+    if a.full and not a.no_extras:
         run_extras()
     milestone("done")
     if rank == 0:
@@ -895,6 +915,37 @@ def replica_digest(eng, gpu: bool) -> str:
     for b in bufs:
         h.update(b.detach().cpu().contiguous().view(torch.uint8).numpy().tobytes())
     return h.hexdigest()[:48]
+
+
+# --dump-outputs: at most this many elements of one array (three arrays of 4 Mi fp32 elements:
+# 48 MiB in all); a larger array is written as a seeded sample of its elements
+DUMP_MAX_ELEMS = 4 << 20
+DUMP_SEED = 0
+
+
+def dump_outputs(out_dir: str, eng, loss: float) -> None:
+    """What the last timed step left, as float32 / float64 ``.npy`` files in ``out_dir``:
+    ``master`` (fp32 parameters, the arena's flat layout), ``momentum``, ``shadow`` (the bf16
+    weights the next forward reads, widened to float32; bf16 runs only) and ``loss`` (float64,
+    one element).  An array above DUMP_MAX_ELEMS elements is sampled at sorted positions drawn
+    once from a generator seeded with DUMP_SEED and the array's length, so two runs of the same
+    job write the same positions."""
+    import numpy as np
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    eng.synchronize()
+    ar = eng.arena
+    arrays = {"master": ar.master, "momentum": ar.momentum}
+    if ar.shadow is not None:
+        arrays["shadow"] = ar.shadow
+    for name, t in arrays.items():
+        t = t.detach().reshape(-1)
+        if t.numel() > DUMP_MAX_ELEMS:
+            rng = np.random.default_rng([DUMP_SEED, t.numel()])
+            idx = np.sort(rng.integers(0, t.numel(), size=DUMP_MAX_ELEMS, dtype=np.int64))
+            t = t[torch.from_numpy(idx).to(t.device)]
+        np.save(os.path.join(out_dir, name + ".npy"), t.to(torch.float32).cpu().numpy())
+    np.save(os.path.join(out_dir, "loss.npy"), np.asarray([loss], dtype=np.float64))
 
 
 def _trace(msg: str):

@@ -30,7 +30,7 @@ def _line(r):
 
 def test_bench_self_launches_two_ranks_cpu():
     d = _line(_run(["--gpus", "2", "--device", "cpu", "--config", "ref", "--steps", "10",
-                    "--warmup", "2"]))
+                    "--warmup", "2", "--full"]))
     assert d["n_gpus"] == 2 and d["config"]["parallelism"] == "dp2"
     assert d["steps"] == 10 and d["warmup"] == 2
     assert d["config"]["comm"] == "gloo" and d["config"]["uneven_split"]
@@ -45,10 +45,69 @@ def test_bench_self_launches_two_ranks_cpu():
 
 
 def test_bench_single_rank_cpu_unchanged_shape():
-    d = _line(_run(["--device", "cpu", "--config", "ref", "--steps", "10", "--warmup", "2"]))
+    d = _line(_run(["--device", "cpu", "--config", "ref", "--steps", "10", "--warmup", "2",
+                    "--full"]))
     assert d["n_gpus"] == 1 and d["config"]["parallelism"] == "dp1"
     assert d["config"]["comm"] == "none" and d["parallel_efficiency"] == 1.0
     assert d["strong_scaling"] is None
+
+
+EXTRAS_FIELDS = ("parallel_efficiency", "single_gpu_samples_per_s", "single_gpu_ms_per_step",
+                 "exposed_comm_ms", "comm_only_ms", "overlap_pct", "comm_bus_gbps",
+                 "strong_scaling")
+
+
+def _check_dump(d, out_dir, n_arrays):
+    import numpy as np
+    files = sorted(os.listdir(out_dir))
+    assert files == sorted(n + ".npy" for n in n_arrays), files
+    arrs = {n: np.load(os.path.join(out_dir, n + ".npy")) for n in n_arrays}
+    assert all(a.dtype in (np.float32, np.float64) for a in arrs.values())
+    assert sum(a.nbytes for a in arrs.values()) <= 64 * 2 ** 20
+    assert all(np.isfinite(a).all() for a in arrs.values())
+    assert arrs["loss"].shape == (1,) and float(arrs["loss"][0]) == d["final_loss"]
+    assert arrs["master"].shape == arrs["momentum"].shape and arrs["master"].size > 0
+    assert np.abs(arrs["momentum"]).max() > 0          # steps ran: the momentum holds gradients
+    return arrs
+
+
+def test_bench_plain_run_skips_the_extras_and_dumps_its_outputs(tmp_path):
+    """A plain run (no --full) times its steps and nothing else: the extras' fields are null on
+    two ranks too; --dump-outputs writes the last step's parameters, momentum and loss, and a
+    second run with the same arguments writes the same arrays."""
+    import numpy as np
+    args = ["--gpus", "2", "--device", "cpu", "--config", "ref", "--steps", "5", "--warmup", "2"]
+    d = _line(_run(args + ["--dump-outputs", str(tmp_path / "a")]))
+    assert d["steps"] == 5 and d["ms_per_step"] > 0 and d["extras_error"] is None
+    for k in EXTRAS_FIELDS:
+        assert d[k] is None, k
+    a = _check_dump(d, tmp_path / "a", ("master", "momentum", "loss"))
+    _line(_run(args + ["--dump-outputs", str(tmp_path / "b")]))
+    b = _check_dump(d, tmp_path / "b", ("master", "momentum", "loss"))
+    for k in a:
+        assert np.array_equal(a[k], b[k]), k
+
+
+def test_bench_dump_samples_a_large_array_at_fixed_positions(tmp_path, monkeypatch):
+    """An array above the per-array cap is written as the same sorted sample every time."""
+    import types
+    import numpy as np
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    monkeypatch.setattr(bench, "DUMP_MAX_ELEMS", 100)
+    big = torch.arange(1000, dtype=torch.float32)
+    arena = types.SimpleNamespace(master=big, momentum=-big, shadow=big[:50].to(torch.bfloat16))
+    eng = types.SimpleNamespace(arena=arena, synchronize=lambda: None)
+    for sub in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / sub), eng, 1.5)
+    m = np.load(tmp_path / "a" / "master.npy")
+    assert m.shape == (100,) and m.dtype == np.float32 and (np.diff(m) >= 0).all()
+    assert np.array_equal(np.load(tmp_path / "a" / "momentum.npy"), -m)   # the same positions
+    assert np.array_equal(m, np.load(tmp_path / "b" / "master.npy"))
+    s = np.load(tmp_path / "a" / "shadow.npy")
+    assert s.dtype == np.float32 and np.array_equal(s, np.arange(50, dtype=np.float32))
+    assert np.load(tmp_path / "a" / "loss.npy").tolist() == [1.5]
 
 
 def test_bench_refuses_world_mismatch_under_launcher():
@@ -69,7 +128,7 @@ def test_bench_rank_sigsegv_relaunches_fresh_ranks():
     result: the supervisors kill the attempt's survivors and re-run the job in fresh processes
     with the inline schedule; the line says why (fallback) and which mode produced it."""
     d = _line(_run(["--gpus", "2", "--device", "cpu", "--config", "ref", "--steps", "6",
-                    "--warmup", "2"], env={"NNMPI_BENCH_CRASH": "1:0"}))
+                    "--warmup", "2", "--full"], env={"NNMPI_BENCH_CRASH": "1:0"}))
     assert "SIGSEGV" in d["fallback"] and d["measured_mode"] == "--comm_mode inline"
     assert [e["result"] for e in d["attempts"]] == ["none", "full"]
     assert d["replicas_bitwise_equal"] is True and d["extras_error"] is None
@@ -79,7 +138,8 @@ def test_bench_rank_hang_is_detected_and_retried():
     """A rank that stops making progress (a peer blocked forever in a collective) is killed after
     the stall limit, and so is the rest of the attempt."""
     d = _line(_run(["--gpus", "3", "--device", "cpu", "--config", "ref", "--steps", "6",
-                    "--warmup", "2"], env={"NNMPI_BENCH_HANG": "2:0", "NNMPI_BENCH_STALL_S": "8"}))
+                    "--warmup", "2", "--full"],
+                   env={"NNMPI_BENCH_HANG": "2:0", "NNMPI_BENCH_STALL_S": "8"}))
     assert "no progress" in d["fallback"] and d["attempts"][-1]["result"] == "full"
     assert d["n_gpus"] == 3 and d["replicas_bitwise_equal"] is True
 
@@ -87,7 +147,7 @@ def test_bench_rank_hang_is_detected_and_retried():
 def test_bench_crash_in_extras_keeps_the_measurement_under_torchrun():
     """Rank 0 dying after the timed region (inside the efficiency extras), under the driver's
     torchrun form: the timed measurement is still printed, with extras_error, and rc 0."""
-    r = _torchrun(["--steps", "6", "--warmup", "2"],
+    r = _torchrun(["--steps", "6", "--warmup", "2", "--full"],
                   env={"NNMPI_BENCH_CRASH": "0:0:extras single_gpu"})
     d = _line(r)
     assert d["extras_error"] and d["parallel_efficiency"] is None
@@ -131,12 +191,32 @@ def test_bench_more_gpus_than_visible_fails():
 
 @pytest.mark.gpu
 @pytest.mark.rowband
+def test_bench_plain_gpu_run_dumps_the_last_steps_state(tmp_path):
+    """The driver's plain 1-GPU run with --dump-outputs: exactly --steps timed steps, no extras,
+    and the bf16 proxy's master / momentum / shadow / loss written as float arrays."""
+    import numpy as np
+    d = _line(_run(["--gpus", "1", "--steps", "7", "--warmup", "2", "--dump-outputs",
+                    str(tmp_path)], timeout=120))
+    assert d["steps"] == 7 and d["ms_per_step"] > 0 and d["dtype"] == "bf16"
+    assert d["value"] == pytest.approx(8192 / (d["ms_per_step"] * 1e-3), rel=1e-3)
+    for k in EXTRAS_FIELDS:
+        assert d[k] is None, k
+    a = _check_dump(d, tmp_path, ("master", "momentum", "shadow", "loss"))
+    n_params = 3 * (512 * 512 + 512) + 512 + 1
+    assert a["master"].size >= n_params and a["shadow"].dtype == np.float32
+    # the shadow is the bf16 rounding of the master weights it mirrors: within 2^-8 relative
+    k = min(a["shadow"].size, a["master"].size)
+    assert np.abs(a["shadow"][:k] - a["master"][:k]).max() <= 2.0 ** -8 * np.abs(a["master"]).max()
+
+
+@pytest.mark.gpu
+@pytest.mark.rowband
 def test_bench_two_rank_rehearsal_on_one_gpu():
     """The whole multi-rank bench path -- tune of inline / ZeRO-1 / overlap schedules with the
     RCCL collectives captured in hipGraphs, timed region, efficiency / comm-only / strong-scaling
     extras -- with 2 RCCL ranks sharing the one GPU (NCCL_HOSTID rehearsal mode)."""
     r = _run(["--gpus", "2", "--shared_gpu_rehearsal", "--steps", "8", "--warmup", "2",
-              "--tune_steps", "4"], timeout=300)
+              "--tune_steps", "4", "--full"], timeout=300)
     d = _line(r)
     assert d["n_gpus"] == 2 and d["rccl_ranks"] == 2 and d["shared_gpu_rehearsal"]
     mode = d["config"]["comm_mode"]
@@ -221,8 +301,8 @@ def test_bench_driver_torchrun_form_on_one_gpu():
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1",
                         "--nproc-per-node", "2", "--master-addr", "127.0.0.1", "--master-port",
                         str(free_port()), BENCH, "--gpus", "2", "--steps", "8", "--warmup", "2",
-                        "--tune_steps", "4", "--shared_gpu_rehearsal"], capture_output=True,
-                       text=True, timeout=300, env=e)
+                        "--tune_steps", "4", "--shared_gpu_rehearsal", "--full"],
+                       capture_output=True, text=True, timeout=300, env=e)
     d = _line(r)
     assert d["n_gpus"] == 2 and d["rccl_ranks"] == 2 and d["replicas_bitwise_equal"] is True
     assert d["fallback"] is None and d["attempts"][0]["result"] == "full"
@@ -256,13 +336,13 @@ def _torchrun(args, n=2, env=None):
 def test_bench_under_torchrun_driver_command():
     """The driver's exact launch form: torch.distributed.run --nnodes=1 --nproc-per-node N
     --master-addr 127.0.0.1 --master-port P bench.py --gpus N (CPU plumbing here)."""
-    d = _line(_torchrun(["--steps", "6", "--warmup", "2"]))
+    d = _line(_torchrun(["--steps", "6", "--warmup", "2", "--full"]))
     assert d["n_gpus"] == 2 and d["steps"] == 6 and d["config"]["parallelism"] == "dp2"
     assert d["replicas_bitwise_equal"] is True and d["fallback"] is None
 
 
 def test_bench_under_torchrun_sigsegv_falls_back():
-    d = _line(_torchrun(["--steps", "6", "--warmup", "2"], n=3,
+    d = _line(_torchrun(["--steps", "6", "--warmup", "2", "--full"], n=3,
                         env={"NNMPI_BENCH_CRASH": "2:0:warm-up"}))
     assert "rank 2 killed by SIGSEGV" == d["fallback"] and d["n_gpus"] == 3
 
