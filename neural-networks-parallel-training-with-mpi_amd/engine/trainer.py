@@ -276,7 +276,6 @@ def make_ops(j: Job):
     if j.device.type == "cuda":
         from ..ops.hip_ops import HipOps
         return HipOps(j.device)
-    from ..ops.torch_ops import TorchOps
     return cpu_ops(j.device)
 
 
@@ -306,7 +305,7 @@ def loss_scales(cfg: TrainConfig, rows_local: int, rows_all: List[int], out_f: i
 
 def _gather_state(eng, sync):
     """Sharded optimizer: re-assemble the full fp32 master + momentum on every rank (collective)."""
-    if getattr(sync, "sharded", False):
+    if sync.sharded:
         eng.synchronize()
         sync.gather_state()
 
@@ -418,7 +417,7 @@ def _run(j: Job) -> TrainResult:
     Xc = X.to(dtype)
     metrics = MetricsWriter(cfg.metrics_json if rank == 0 else None)
     cvol = comm_volume(arena.numel, world, grad_payload(cfg, j.device.type, arena.numel),
-                       sharded=getattr(sync, "sharded", False),
+                       sharded=sync.sharded,
                        shadow=arena.shadow is not None)
     seqchk = SequenceChecker(j.pg) if cfg.seqcheck else None
     if seqchk is not None:

@@ -1,0 +1,31 @@
+"""What every op set answers when the engine asks what it can do: the engine picks its schedule
+from these predicates and size queries.  An op set overrides the ones whose kernels it has;
+everything else keeps the "not supported" answer declared here (TorchOps keeps all of them)."""
+from __future__ import annotations
+
+
+def _no(*args, **kw) -> bool:
+    return False
+
+
+def _zero(*args, **kw) -> int:
+    return 0
+
+
+def yes(*args, **kw) -> bool:
+    return True
+
+
+class OpSet:
+    # the op set has tiny_step / sgd_fusion / the weight gradients that store the bf16
+    # all-reduce payload themselves (linear_wgrad(out_bf16=), linear_wgrad_defer)
+    tiny_supported = can_fuse_sgd = can_write_bf16_wgrad = _no
+    # per-shape predicates
+    tiny_can_fuse_sgd = bwd_group_supported = wide_pair_wgrad_ok = rowband_split_ok = _no
+    # workspace sizes in bytes; the row-band kernel version that runs a model (0: none)
+    tiny_workspace_bytes = wgrad_workspace_bytes = head_workspace_bytes = rowband_version = _zero
+
+    def rowband_ok(self, rows, widths, act, loss) -> bool:
+        """The whole forward + head + activation-gradient chain runs as one launch per step
+        (see rowband.hip)."""
+        return self.rowband_version(rows, widths, act, loss) > 0

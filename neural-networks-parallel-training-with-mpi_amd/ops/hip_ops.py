@@ -6,13 +6,13 @@ captured into a hipGraph).  Workspaces are provided by the caller (the engine si
 """
 from __future__ import annotations
 
-import os
 from typing import Optional, Tuple
 
 import torch
 from ..utils.knobs import knob
 
 from .. import native
+from .base import OpSet, yes
 from .torch_ops import ACT_CODES
 
 LOSS_CODES = {"mse": 0, "xent": 1}
@@ -27,8 +27,9 @@ def _check(cond, msg):
         raise ValueError(msg)
 
 
-class HipOps:
+class HipOps(OpSet):
     name = "hip"
+    tiny_supported = can_fuse_sgd = can_write_bf16_wgrad = yes   # (see OpSet)
 
     def __init__(self, device="cuda"):
         self.device = torch.device(device)
@@ -330,11 +331,6 @@ class HipOps:
         H, in_, nh, out = widths[1], widths[0], len(widths) - 2, widths[-1]
         lc, ac = LOSS_CODES.get(loss, -1), ACT_CODES[act]
         return 2 if self.lib.rowband2_ok(int(rows), H, in_, nh, out, lc, ac) else 0
-
-    def rowband_ok(self, rows: int, widths, act: str, loss: str) -> bool:
-        """The whole forward + head + activation-gradient chain runs as one launch per step
-        (see rowband.hip)."""
-        return self.rowband_version(rows, widths, act, loss) > 0
 
     def rowband_split_ok(self, rows: int, H: int, in_: int, nh: int, act: str = "relu") -> bool:
         """A row-band step of ``rows`` rows runs the column-split kernel (rowband.hip

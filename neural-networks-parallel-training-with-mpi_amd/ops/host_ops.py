@@ -12,10 +12,10 @@ numerics oracle (``NNMPI_EXPERIMENTS=1 NNMPI_CPU_NATIVE=0`` selects it for tiny 
 from __future__ import annotations
 
 from ..utils.knobs import knob
-import os
 
 from .. import native
 from .hip_ops import LOSS_CODES
+from .base import yes
 from .torch_ops import ACT_CODES, TorchOps
 
 
@@ -35,11 +35,7 @@ class HostOps(TorchOps):
         self.lib = native.lib()
 
     # ---------------- whole tiny step ----------------
-    def tiny_workspace_bytes(self, rows, numel) -> int:
-        return 0
-
-    def tiny_can_fuse_sgd(self, rows: int) -> bool:
-        return True
+    tiny_supported = can_fuse_sgd = tiny_can_fuse_sgd = yes   # (see OpSet)
 
     @staticmethod
     def sgd_fusion(arena, hp, nesterov: bool, first: bool):

@@ -13,6 +13,8 @@ from __future__ import annotations
 
 import torch
 
+from .base import OpSet
+
 ACT_CODES = {"none": 0, "relu": 1, "tanh": 2}
 
 
@@ -32,7 +34,7 @@ def act_bwd_from_out(a: torch.Tensor, act: str) -> torch.Tensor:
     return torch.ones_like(a)
 
 
-class TorchOps:
+class TorchOps(OpSet):
     name = "torch"
 
     def __init__(self, device="cpu"):

@@ -52,6 +52,7 @@ def _subtract(rng, cuts):
 
 class GradSync:
     world = 1
+    sharded = False   # True: the optimizer state is sharded, update() replaces the SGD pass
 
     def __init__(self, arena):
         self.arena = arena
