@@ -65,6 +65,8 @@ int tiny_mlp_step_host(const TinyMLPDesc& d, float* P, const float* X, const flo
   if (L < 1 || L > HL) return 1;
   for (int l = 0; l <= L; ++l)
     if (d.widths[l] < 1 || d.widths[l] > HW) return 1;
+  // hidden layers take relu / tanh only, as the GPU launcher (tiny_mlp.hip) does
+  if (L > 1 && d.act != 1 && d.act != 2) return 1;
   // the model occupies arena[w_off[L-1] .. arena_numel) (reverse layer order, W_{L-1} first)
   const int base = d.w_off[L - 1];
   std::fill(grad + base, grad + arena_numel, 0.f);
@@ -101,7 +103,7 @@ int tiny_mlp_step_host(const TinyMLPDesc& d, float* P, const float* X, const flo
       const float lse = mx + std::log(se);
       const int lab = (int)labels[r];
       for (int o = 0; o < out_w; ++o)
-        delta[o] = (std::exp(z[o] - lse) - (o == lab ? 1.f : 0.f)) * inv_count;
+        delta[o] = (std::exp(z[o] - mx) / se - (o == lab ? 1.f : 0.f)) * inv_count;
       row_loss = lse - z[lab];
     }
     loss += row_loss;

@@ -168,7 +168,7 @@ __global__ void __launch_bounds__(64 * HW) head_fwd_kernel(HeadArgs p, float* __
 #pragma unroll
         for (int o = 0; o < OUTM; ++o) {
           if (o == lab) lgl = lg[o];
-          dl[o] = (o < nout) ? (__expf(lg[o] - lse) - (o == lab ? 1.f : 0.f)) * p.inv_count : 0.f;
+          dl[o] = (o < nout) ? (__expf(lg[o] - mx) / se - (o == lab ? 1.f : 0.f)) * p.inv_count : 0.f;
         }
         row_loss = lse - lgl;
       }
@@ -410,7 +410,7 @@ __global__ void __launch_bounds__(64 * MH_WAVES) head_mfma_kernel(HeadArgs p) {
       for (int j = 0; j < 4; ++j) {
         const int n = 4 * g + j;
         if (n == lab) picked = z[j];
-        dl[j] = (n < out && valid) ? (__expf(z[j] - lse) - (n == lab ? 1.f : 0.f)) * p.inv_count : 0.f;
+        dl[j] = (n < out && valid) ? (__expf(z[j] - mx) / se - (n == lab ? 1.f : 0.f)) * p.inv_count : 0.f;
       }
       picked += __shfl_xor(picked, 16, 64);
       picked += __shfl_xor(picked, 32, 64);
@@ -873,7 +873,7 @@ __global__ void __launch_bounds__(64 * HS_WAVES) head_logits_stream_kernel(
           for (int j = 0; j < 4; ++j) {
             const int n = 16 * t + 4 * g + j;
             if (n == lab) picked = z[t][j];
-            d[t][j] = (n < out && valid) ? (__expf(z[t][j] - lse) - (n == lab ? 1.f : 0.f)) * inv_count : 0.f;
+            d[t][j] = (n < out && valid) ? (__expf(z[t][j] - mx) / se - (n == lab ? 1.f : 0.f)) * inv_count : 0.f;
           }
         picked += __shfl_xor(picked, 16, 64);
         picked += __shfl_xor(picked, 32, 64);

@@ -116,8 +116,10 @@ __global__ void __launch_bounds__(64 * HG_LOSS_ROWS) hg_loss_kernel(float* __res
       s = wave_sum(s);
       const float zl = wave_sum(zlp);   // the label's logit, gathered before any rewrite
       const float lse = m + logf(s);
+      // p = e / s rather than exp(z - lse): lse carries a rounding of |lse| 2^-24 that would scale
+      // the whole row, so that its dl no longer sums to 0 at large logits
       for (int o = lane; o < out; o += 64) {
-        const float p = expf(zr[o] - lse);
+        const float p = expf(zr[o] - m) / s;
         zr[o] = (p - (o == lab ? 1.f : 0.f)) * inv_count;
       }
       loss = lse - zl;

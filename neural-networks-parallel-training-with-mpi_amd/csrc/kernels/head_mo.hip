@@ -217,7 +217,7 @@ __global__ void __launch_bounds__(64 * MF_WAVES) head_mo_fused_kernel(HeadArgs p
       for (int j = 0; j < 4; ++j) {
         const int n = 4 * g + j;
         if (n == lab) picked = z[j];
-        dl[j] = (n < out && valid) ? (__expf(z[j] - lse) - (n == lab ? 1.f : 0.f)) * p.inv_count : 0.f;
+        dl[j] = (n < out && valid) ? (__expf(z[j] - mx) / se - (n == lab ? 1.f : 0.f)) * p.inv_count : 0.f;
       }
       picked += __shfl_xor(picked, 16, 64);
       picked += __shfl_xor(picked, 32, 64);

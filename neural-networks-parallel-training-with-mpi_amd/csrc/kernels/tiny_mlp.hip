@@ -102,12 +102,14 @@ __global__ void __launch_bounds__(256) tiny_mlp_kernel(TinyMLPDesc d, const floa
 #pragma unroll
       for (int o = 0; o < TW; ++o) if (o < out_w) se += __expf(outv[o] - mx);
       const float lse = mx + __logf(se);
+      // (the probabilities are e / se, not exp(z - lse): the rounding of lse, |lse| 2^-24, would
+      // otherwise scale the whole row, and a row's deltas no longer sum to 0 at large logits)
       const int lab = valid ? (int)labels[r] : -1;
       float ll = 0.f;
 #pragma unroll
       for (int o = 0; o < TW; ++o) {
         if (o == lab) ll = outv[o];
-        delta[o] = (valid && o < out_w) ? (__expf(outv[o] - lse) - (o == lab ? 1.f : 0.f)) * inv_count : 0.f;
+        delta[o] = (valid && o < out_w) ? (__expf(outv[o] - mx) / se - (o == lab ? 1.f : 0.f)) * inv_count : 0.f;
       }
       row_loss = valid ? lse - ll : 0.f;
     }
@@ -187,7 +189,11 @@ hipError_t tiny_mlp_step(const TinyMLPDesc& d, const float* params, const float*
   if (d.n_layers < 1 || d.n_layers > TL) return hipErrorInvalidValue;
   for (int l = 0; l <= d.n_layers; ++l)
     if (d.widths[l] < 1 || d.widths[l] > TW) return hipErrorInvalidValue;
+  // a hidden layer needs an activation this file instantiates: "none" (or an unknown code) would
+  // otherwise run the ReLU kernel silently, where the host twin runs the identity
+  if (d.n_layers > 1 && d.act != ACT_RELU && d.act != ACT_TANH) return hipErrorInvalidValue;
   const int nb = tiny_blocks(rows);
+  if (nb > 1 && sgd) return hipErrorInvalidValue;   // the optimizer fusion needs the single-block form
   // the model occupies arena[w_off[L-1] .. arena_numel) (reverse layer order, W_{L-1} first)
   const int base = d.w_off[d.n_layers - 1];
   const int numel = arena_numel - base;
@@ -222,7 +228,6 @@ hipError_t tiny_mlp_step(const TinyMLPDesc& d, const float* params, const float*
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return e;
   if (nb > 1) {
-    if (sgd) return hipErrorInvalidValue;   // the optimizer fusion needs the single-block form
     return splitk_reduce(slabs, nb, numel, 1, numel, grad + base, numel, nullptr, 0, nullptr,
                          loss_part, nb, loss_scale, loss_out, s);
   }

@@ -359,6 +359,29 @@ def test_gather_rows_kernel():
         dst = torch.zeros((80,) + tuple(src.shape[1:]), dtype=src.dtype, device=DEV)
         ops.gather_rows(src, idx, dst)
         assert torch.equal(dst[:77], src[idx])
+    # out-of-range indices are clamped to the first / last row of the shard
+    src = torch.randn(100, 37, device=DEV)
+    wild = torch.tensor([-5, 100 + 3, 0, 99, -1, 2 ** 40], device=DEV)
+    dst = torch.full((8, 37), 5.0, device=DEV)
+    ops.gather_rows(src, wild, dst)
+    assert torch.equal(dst[:6], src[torch.tensor([0, 99, 0, 99, 0, 99], device=DEV)])
+    assert (dst[6:] == 5.0).all(), "destination rows past n must stay untouched"
+    # more rows than the grid has waves (2,048 blocks x 4), 4-byte and 20-byte rows
+    n = 8200
+    big = torch.randint(0, 100, (n,), generator=g).to(DEV)
+    for src in (torch.arange(100, device=DEV, dtype=torch.int32), torch.randn(100, 5, device=DEV)):
+        dst = torch.full((n + 3,) + tuple(src.shape[1:]), 5, dtype=src.dtype, device=DEV)
+        ops.gather_rows(src, big, dst)
+        assert torch.equal(dst[:n], src[big])
+        assert (dst[n:] == 5).all(), "destination rows past n must stay untouched"
+    # 48-byte rows into a destination that starts 4 bytes into its buffer: the 4-byte path
+    src = torch.randn(100, 12, device=DEV)
+    buf = torch.full((1 + 80 * 12,), 5.0, device=DEV)
+    dst = buf[1:].view(80, 12)
+    assert dst.data_ptr() % 16 == 4
+    ops.gather_rows(src, idx, dst)
+    assert torch.equal(dst[:77], src[idx])
+    assert buf[0] == 5.0 and (dst[77:] == 5.0).all()
 
 
 def test_minibatch_training_gpu_matches_cpu():
