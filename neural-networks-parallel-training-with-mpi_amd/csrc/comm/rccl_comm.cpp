@@ -183,6 +183,25 @@ void RcclComm::allreduce_f32_ordered(void* buf, void* scratch, size_t count, hip
   NCCL_THROW(ncclGroupEnd());
 }
 
+// The reduce-scatter leg of ZeRO-1 with the sums of allreduce_f32_ordered: rank r ends with
+// slice r of `buf` (nranks slices of `shard` elements) summed over the ranks in rank order, in
+// place -- bit for bit what the ordered all-reduce leaves there (ncclReduceScatter's ring sums
+// slice r in the order r+1, r+2, ..., r).  scratch: nranks * shard floats.
+void RcclComm::reduce_scatter_f32_ordered(void* buf, void* scratch, size_t shard, hipStream_t s) {
+  if (nranks_ == 1 || shard == 0) return;
+  float* b = static_cast<float*>(buf);
+  float* sc = static_cast<float*>(scratch);
+  NCCL_THROW(ncclGroupStart());
+  for (int q = 0; q < nranks_; ++q) {
+    if (q == rank_) continue;
+    NCCL_THROW(ncclSend(b + (size_t)q * shard, shard, ncclFloat32, q, comm_, s));
+    NCCL_THROW(ncclRecv(sc + (size_t)q * shard, shard, ncclFloat32, q, comm_, s));
+  }
+  NCCL_THROW(ncclGroupEnd());
+  HIP_THROW(sum_slices_f32(b + (size_t)rank_ * shard, sc, nranks_, rank_, (long long)shard,
+                           (long long)shard, s));
+}
+
 int RcclComm::poll_error(bool abort_on_error) {
   if (aborted_) return (int)ncclInvalidUsage;
   ncclResult_t r = ncclSuccess;

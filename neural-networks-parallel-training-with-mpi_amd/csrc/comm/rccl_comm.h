@@ -62,6 +62,8 @@ class RcclComm {
   // step.  Bitwise independent of how a gradient is cut into buckets.  scratch: at least
   // acc32_scratch_elems(count) floats.
   void allreduce_f32_ordered(void* buf, void* scratch, size_t count, hipStream_t s);
+  // ZeRO-1's reduce-scatter with the same rank-ordered sums (in place: rank r's slice of buf)
+  void reduce_scatter_f32_ordered(void* buf, void* scratch, size_t shard, hipStream_t s);
   size_t acc32_scratch_elems(size_t count) const { return acc32_slice(count) * nranks_; }
   // Returns the RCCL async error code (0 = ok); aborts the communicator on error if asked.
   int poll_error(bool abort_on_error);

@@ -166,6 +166,35 @@ __device__ __forceinline__ f32x4 sgd_fused_store4(const SgdFuse& f, const float*
   return p;
 }
 
+// torch.optim.Adam / AdamW update of one element (adam.py / adamw.py semantics, no amsgrad, no
+// maximize).  The hyper-parameters come from the Adam layout of the hyper-parameter tensor
+// (optim.hip): adam_hp() reads it once per thread and derives the two per-step scalars.
+// Contraction is pinned as in sgd_elem, so every launch shape rounds identically.
+struct AdamHp {
+  float lr, b1, b2, wd, gs, eps, omb1, omb2;
+  float step;    // lr / bc1
+  float bc2s;    // sqrt(bc2)
+};
+__device__ __forceinline__ AdamHp adam_hp(const float* __restrict__ hp) {
+#pragma clang fp contract(off)
+  AdamHp h;
+  h.lr = hp[ADAM_LR]; h.b1 = hp[ADAM_B1]; h.b2 = hp[ADAM_B2]; h.wd = hp[ADAM_WD];
+  h.gs = hp[ADAM_GS]; h.eps = hp[ADAM_EPS]; h.omb1 = hp[ADAM_OMB1]; h.omb2 = hp[ADAM_OMB2];
+  h.step = h.lr / hp[ADAM_BC1];
+  h.bc2s = sqrtf(hp[ADAM_BC2]);
+  return h;
+}
+__device__ __forceinline__ float adam_elem(float p, float g, float& m, float& v, const AdamHp& h,
+                                           bool decoupled) {
+#pragma clang fp contract(off)
+  float d = g * h.gs;
+  if (decoupled) p *= 1.f - h.lr * h.wd;         // AdamW: the decay acts on the weight itself
+  else if (h.wd != 0.f) d = fmaf(h.wd, p, d);    // Adam: L2 term folded into the gradient
+  m = fmaf(h.b1, m, h.omb1 * d);
+  v = fmaf(h.b2, v, (h.omb2 * d) * d);
+  return fmaf(-h.step, m / (sqrtf(v) / h.bc2s + h.eps), p);
+}
+
 // Element offset of (row n, column k) of a [N][K] bf16 matrix (K % 32 == 0) in its FRAGMENT-MAJOR
 // image (rowband.hip v2): fragment (n >> 4, k >> 5) is 1 KiB, the v_mfma_f32_16x16x32_bf16
 // operand map -- lane (n & 15) + 16 * ((k >> 3) & 3) holds its 8 consecutive k at (k & 7).

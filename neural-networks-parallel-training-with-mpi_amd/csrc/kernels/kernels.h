@@ -15,6 +15,9 @@ constexpr int RB_MAXL_PK = 4;   // == RB_MAXL (row-band hidden layers), see belo
 // Optional optimizer fusion for kernels that produce final (already reduced) gradients: the
 // parameter / momentum / bf16-shadow arrays share the gradient arena's layout, so an element's
 // position is found from its offset to g_base.  g_base == nullptr disables the fusion.
+// SGD-momentum only: the fused epilogues carry one state buffer and sgd_elem.  Adam / AdamW
+// (two state buffers, a per-step bias correction) never pass an SgdFuse -- the engine takes the
+// unfused form of every schedule and applies adam_update as a separate pass behind the gradient.
 struct SgdFuse {
   const float* g_base;
   float* p_base;
@@ -380,6 +383,25 @@ hipError_t sgd_momentum_bg(float* p, float* g, float* buf, bf16* shadow, long lo
 hipError_t sgd_momentum_bf16grad(float* p, const bf16* g, float* buf, bf16* shadow, long long n,
                                  const float* hp, int nesterov, int first, hipStream_t s,
                                  const SgdPack* pack = nullptr);
+// ---- Adam / AdamW (optim.hip: the layout comment at its top) ----
+// Slots of the hyper-parameter tensor under Adam (ADAM_HP_LEN floats).  0, 3 and 4 keep their
+// SGD meaning; bc1 / bc2 are written on the device by adam_tick, everything else by the host.
+enum AdamSlot : int {
+  ADAM_LR = 0, ADAM_B1 = 1, ADAM_B2 = 2, ADAM_WD = 3, ADAM_GS = 4, ADAM_EPS = 5, ADAM_BC1 = 6,
+  ADAM_BC2 = 7, ADAM_OMB1 = 8, ADAM_OMB2 = 9, ADAM_B1_LO = 10, ADAM_B2_LO = 11, ADAM_HP_LEN = 12
+};
+// One pass over n elements (n % 4 == 0): master p, fp32 gradient g (zeroed behind the pass when
+// zero_grad), exp_avg m, exp_avg_sq v, the bf16 shadow (may be null), the row-band images of
+// `pack` (element-wise refresh).  decoupled: AdamW, else Adam's L2 weight decay.
+hipError_t adam_update(float* p, float* g, float* m, float* v, bf16* shadow, long long n,
+                       const float* hp, int decoupled, int zero_grad, hipStream_t s,
+                       const SgdPack* pack = nullptr);
+// the same update with the gradient read from a bf16 buffer (the bf16 all-reduce payload)
+hipError_t adam_update_bf16grad(float* p, const bf16* g, float* m, float* v, bf16* shadow,
+                                long long n, const float* hp, int decoupled, hipStream_t s,
+                                const SgdPack* pack = nullptr);
+// ++*t (an int32 in device memory), then hp[ADAM_BC1] = 1 - beta1^t, hp[ADAM_BC2] = 1 - beta2^t
+hipError_t adam_tick(float* hp, int* t, hipStream_t s);
 hipError_t cast_f32_bf16(const float* x, bf16* y, long long n, hipStream_t s);
 hipError_t scale_f32(float* x, long long n, float a, hipStream_t s);
 hipError_t cast_bf16_f32(const bf16* x, float* y, long long n, hipStream_t s);

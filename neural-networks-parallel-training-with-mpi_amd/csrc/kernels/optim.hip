@@ -6,6 +6,21 @@
 // dampening / Nesterov, the update of the fp32 master weights, the refresh of the bf16 compute
 // shadow, and zeroes the gradient for the next step.  16-byte vector accesses, grid-stride.
 // Hyper-parameters are read from device memory so a captured hipGraph picks up LR changes.
+//
+// adam_update is the same kind of pass for torch.optim.Adam / AdamW: it reads p, g, exp_avg,
+// exp_avg_sq and writes p, both states, the bf16 shadow and the zeroed gradient.  Its
+// hyper-parameter tensor has ADAM_HP_LEN = 12 fp32 slots (AdamSlot, kernels.h):
+//
+//    0 lr            3 weight decay    4 gradient scale       -- as under SGD
+//    1 beta1         2 beta2           5 eps
+//    6 bc1 = 1 - beta1^t               7 bc2 = 1 - beta2^t    -- written by adam_tick
+//    8 1 - beta1     9 1 - beta2       -- rounded from the host's doubles (1.f - 0.999f is off
+//                                         by 5e-5 relative)
+//   10, 11  beta1 - fp32(beta1), beta2 - fp32(beta2): adam_tick rebuilds the host's doubles
+//
+// The step number t is an int32 in device memory (a float stops counting at 2^24): adam_tick
+// advances it and refreshes bc1 / bc2 once per optimizer step, as a node of the step's graph, so
+// a replayed graph of N steps advances t N times; the update kernels read only the tensor.
 #include "common.h"
 #include "kernels.h"
 #include "knobs.h"
@@ -277,6 +292,93 @@ hipError_t sgd_momentum_bf16grad(float* p, const bf16* g, float* buf, bf16* shad
     return sgd_tiles_launch<const bf16>(p, g, buf, shadow, n, hp, nesterov, first, 0, j, rt, s);
   hipLaunchKernelGGL(sgd_kernel<const bf16>, dim3(grid_for(n / 4)), dim3(256), 0, s, p, g, buf,
                      shadow, n / 4, hp, nesterov, first, 0, pk);
+  return hipGetLastError();
+}
+
+// Adam / AdamW over the arena, in the shape of sgd_kernel: grid-stride, 16-byte accesses, TG =
+// const bf16 reads the bf16 all-reduce payload and leaves the fp32 gradient alone.  The loads of
+// p, g, m and v are unconditional and independent of the hyper-parameter loads (one round trip
+// per element, see sgd_kernel); 34 bytes move per element with the shadow and the zero-behind
+// (SGD-momentum: 26).  The row-band images are refreshed element-wise (rb_pack_store4).
+template <typename TG>
+__global__ void __launch_bounds__(256) adam_kernel(float* __restrict__ p, TG* __restrict__ g,
+                                                   float* __restrict__ m, float* __restrict__ v,
+                                                   bf16* __restrict__ shadow, long long n4,
+                                                   const float* __restrict__ hp, int decoupled,
+                                                   int zero_grad, SgdPack pk) {
+  const AdamHp h = adam_hp(hp);
+  const long long stride = (long long)gridDim.x * blockDim.x;
+  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride) {
+    f32x4 pv = reinterpret_cast<f32x4*>(p)[i];
+    const f32x4 gv = load_grad4(g, i);
+    f32x4 mv = reinterpret_cast<f32x4*>(m)[i];
+    f32x4 vv = reinterpret_cast<f32x4*>(v)[i];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      float mm = mv[r], ss = vv[r];
+      pv[r] = adam_elem(pv[r], gv[r], mm, ss, h, decoupled != 0);
+      mv[r] = mm;
+      vv[r] = ss;
+    }
+    reinterpret_cast<f32x4*>(m)[i] = mv;
+    reinterpret_cast<f32x4*>(v)[i] = vv;
+    reinterpret_cast<f32x4*>(p)[i] = pv;
+    if (shadow) {
+      bf16x4 s;
+#pragma unroll
+      for (int r = 0; r < 4; ++r) s[r] = (bf16)pv[r];
+      reinterpret_cast<bf16x4*>(shadow)[i] = s;
+    }
+    if constexpr (sizeof(TG) == 4) {
+      if (zero_grad) reinterpret_cast<f32x4*>(g)[i] = f32x4{0.f, 0.f, 0.f, 0.f};
+    }
+    for (int t = 0; t < pk.n; ++t) {   // row-band v2 weight images of the updated weights
+      const long long loc = i * 4 - pk.start[t];
+      if (loc >= 0 && loc < (long long)pk.M[t] * pk.N[t]) {
+        const int r = (int)(loc / pk.N[t]), c = (int)(loc % pk.N[t]);
+        rb_pack_store4(pk.pkf[t], pk.pkd[t], r, c, pk.M[t], pk.N[t], pv);
+      }
+    }
+  }
+}
+
+// One thread: the step counter and the two bias corrections, in double as torch computes them
+// (beta = its fp32 value + the stored remainder: the host's double to 2^-48).
+__global__ void adam_tick_kernel(float* __restrict__ hp, int* __restrict__ t) {
+  if (blockIdx.x != 0 || threadIdx.x != 0) return;
+  const int step = *t + 1;
+  *t = step;
+  const double b1 = (double)hp[ADAM_B1] + (double)hp[ADAM_B1_LO];
+  const double b2 = (double)hp[ADAM_B2] + (double)hp[ADAM_B2_LO];
+  hp[ADAM_BC1] = (float)(1.0 - pow(b1, (double)step));
+  hp[ADAM_BC2] = (float)(1.0 - pow(b2, (double)step));
+}
+
+hipError_t adam_update(float* p, float* g, float* m, float* v, bf16* shadow, long long n,
+                       const float* hp, int decoupled, int zero_grad, hipStream_t s,
+                       const SgdPack* pack) {
+  if (n % 4 != 0 || n < 0 || !pack_ok(pack) || !p || !g || !m || !v || !hp)
+    return hipErrorInvalidValue;
+  if (n == 0) return hipSuccess;
+  hipLaunchKernelGGL(adam_kernel<float>, dim3(grid_for(n / 4)), dim3(256), 0, s, p, g, m, v,
+                     shadow, n / 4, hp, decoupled, zero_grad, pack ? *pack : SgdPack{});
+  return hipGetLastError();
+}
+
+hipError_t adam_update_bf16grad(float* p, const bf16* g, float* m, float* v, bf16* shadow,
+                                long long n, const float* hp, int decoupled, hipStream_t s,
+                                const SgdPack* pack) {
+  if (n % 4 != 0 || n < 0 || !pack_ok(pack) || !p || !g || !m || !v || !hp)
+    return hipErrorInvalidValue;
+  if (n == 0) return hipSuccess;
+  hipLaunchKernelGGL(adam_kernel<const bf16>, dim3(grid_for(n / 4)), dim3(256), 0, s, p, g, m, v,
+                     shadow, n / 4, hp, decoupled, 0, pack ? *pack : SgdPack{});
+  return hipGetLastError();
+}
+
+hipError_t adam_tick(float* hp, int* t, hipStream_t s) {
+  if (!hp || !t) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(adam_tick_kernel, dim3(1), dim3(1), 0, s, hp, t);
   return hipGetLastError();
 }
 

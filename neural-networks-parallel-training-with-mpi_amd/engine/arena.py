@@ -1,8 +1,8 @@
 """Flat parameter / gradient / optimizer-state arena.
 
 All parameters of the MLP live in ONE contiguous fp32 buffer (the master weights), with a
-gradient buffer, a momentum buffer and (for bf16 compute) a bf16 shadow copy of identical
-layout.  Tensors are laid out in **reverse layer order** — ``[W_{L-1}, b_{L-1}, ..., W_0,
+gradient buffer, a momentum buffer (Adam: exp_avg, plus an exp_avg_sq buffer allocated on
+request) and (for bf16 compute) a bf16 shadow copy of identical layout.  Tensors are laid out in **reverse layer order** — ``[W_{L-1}, b_{L-1}, ..., W_0,
 b_0]`` — so the gradients that backward produces first are at the front and every
 communication bucket is one contiguous range in backward order.  Each tensor
 starts on a 64-element (256-byte) boundary so kernels can use 16-byte vector accesses.
@@ -106,6 +106,9 @@ class Arena:
         self.grad = z(torch.float32)
         self.momentum = z(torch.float32)
         self.shadow: Optional[torch.Tensor] = z(shadow_dtype) if shadow_dtype is not None else None
+        # Adam / AdamW: ``momentum`` serves as exp_avg; the second state buffer exists only once
+        # an optimizer asks for it (ensure_exp_avg_sq)
+        self.exp_avg_sq: Optional[torch.Tensor] = None
         self.layer_chunks: Dict[int, int] = {}
         if chunk_layers:
             for li, (out_f, in_f) in enumerate(layer_shapes):
@@ -114,6 +117,18 @@ class Arena:
                 if c > 1:
                     self.layer_chunks[li] = c
         self.buckets = self._plan_buckets(bucket_bytes, grad_elem_bytes)
+
+    # ---- optimizer state ---------------------------------------------------------------
+    @property
+    def exp_avg(self) -> torch.Tensor:
+        """Adam's first moment: the momentum buffer under another name."""
+        return self.momentum
+
+    def ensure_exp_avg_sq(self) -> torch.Tensor:
+        """Adam's second moment, same layout as the master (allocated on the first call)."""
+        if self.exp_avg_sq is None:
+            self.exp_avg_sq = torch.zeros(self.numel, dtype=torch.float32, device=self.device)
+        return self.exp_avg_sq
 
     # ---- views -------------------------------------------------------------------------
     def _view(self, buf: torch.Tensor, slot: Slot) -> torch.Tensor:

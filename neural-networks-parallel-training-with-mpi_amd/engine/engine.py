@@ -12,7 +12,8 @@ One step (per rank), replacing the reference's hot loop ``ref.py:155-211`` (Data
                  dZ_{i-1} = (dZ_i W_i) * act'(h_{i-1})        dgrad + activation backward
     join      compute stream waits for the comm stream
     update    fused SGD-momentum over the whole arena (1/P folded in, bf16 shadow refreshed,
-              gradients zeroed for the next step)
+              gradients zeroed for the next step); or Adam / AdamW, one pass of the same shape
+              behind a one-thread launch that advances the device step number (optimizer.py)
 
 All buffers are allocated once (rows capacity), so on the GPU the steady-state step is
 allocation-free and is captured into ONE hipGraph (kernels + RCCL + cross-stream events) that
@@ -34,6 +35,7 @@ from ..utils.knobs import knob
 from ..models.mlp import MLPSpec
 from ..parallel.sync import NativeRcclSync, NoSync, TorchDistSync
 from .arena import Arena
+from .optimizer import adam_hparams, make_optimizer, sgd_hparams
 from .pipeline import BucketPipeline
 
 TINY_MAX_WIDTH = 16
@@ -83,7 +85,10 @@ class MLPEngine:
                  weight_decay: float = 0.0, nesterov: bool = False, use_graph: bool = True,
                  use_tiny: Optional[bool] = None, overlap: bool = True, fuse_sgd: bool = True,
                  grouped: bool = True, rowband_overlap: bool = False,
-                 rowband_plan: Optional[int] = None):
+                 rowband_plan: Optional[int] = None, optimizer: str = "sgd", beta1: float = 0.9,
+                 beta2: float = 0.999, eps: float = 1e-8):
+        """``optimizer``: ``sgd`` (momentum / dampening / nesterov apply), ``adam`` or ``adamw``
+        (beta1 / beta2 / eps apply; ``momentum`` is ignored).  ``weight_decay`` is shared."""
         self.spec, self.arena, self.ops, self.sync = spec, arena, ops, sync
         self.device = torch.device(device)
         self.dtype = dtype
@@ -115,8 +120,16 @@ class MLPEngine:
         self.dzl = [torch.zeros(R, w[i + 1], dtype=dtype, device=dev) for i in range(L - 1)]
         self.dlogits = torch.zeros(R, w[-1], dtype=torch.float32, device=dev)
         self.loss_out = torch.zeros(4, dtype=torch.float32, device=dev)
-        self.hp = torch.tensor([lr, momentum, dampening, weight_decay, 1.0, 0, 0, 0],
-                               dtype=torch.float32, device=dev)
+        adam = optimizer != "sgd"
+        if adam and (nesterov or dampening):
+            raise ValueError("nesterov / dampening are SGD options: not with " + str(optimizer))
+        self.hp = (adam_hparams(lr, beta1, beta2, eps, weight_decay, dev) if adam else
+                   sgd_hparams(lr, momentum, dampening, weight_decay, dev))
+        # every update site goes through this object (engine/optimizer.py)
+        self.opt = make_optimizer(optimizer, ops, arena, self.hp, self.nesterov)
+        # Adam cannot ride in the kernels' fused epilogues (SgdFuse: one state buffer, the SGD
+        # formula): every schedule runs in its unfused form, the update a separate pass
+        fuse_sgd = bool(fuse_sgd) and self.opt.fusable
         # ---- what the configuration allows; _schedule() picks per batch from these ----------
         self.overlap = bool(overlap) and self.is_cuda and not self.use_tiny
         local = isinstance(sync, NoSync)
@@ -181,15 +194,29 @@ class MLPEngine:
         # the per-bucket collectives and updates of the comm-overlapped bodies
         self.pipe = BucketPipeline(
             spec, arena, ops, sync, self.hp, self.nesterov, self.stream, bf16=bf16,
-            grad16=sync.update_grad() if self.comm_overlap else None, defer=not self.rb_overlap)
+            grad16=sync.update_grad() if self.comm_overlap else None, defer=not self.rb_overlap,
+            opt=self.opt)
         self.rows = 0
-        self.steps_done = 0
+        self._steps = 0
         self._graphs: Dict[tuple, object] = {}
         self.inv_count = 1.0
         self.loss_scale = 1.0
         self.timer = None   # utils.metrics.EventTimer: per-phase breakdown (steps run eagerly)
         self._acc = self._eval_gw = self._loss_hist = None   # allocated on first use
         self._n_acc = 0
+
+    @property
+    def steps_done(self) -> int:
+        """Optimizer steps taken.  Assigning it (a resume) also sets the optimizer's device-side
+        step number; the engine's own bookkeeping advances ``_steps`` -- the device counter
+        advances by itself, once per step, inside the step (Adam.tick)."""
+        return self._steps
+
+    @steps_done.setter
+    def steps_done(self, n: int):
+        self._steps = int(n)
+        with self._on_stream():
+            self.opt.set_step(self._steps)
 
     # names the tests, the trainer and the scripts read
     rb_packed = property(lambda self: self.images.views)
@@ -237,6 +264,8 @@ class MLPEngine:
     def set_hparams(self, lr=None, momentum=None, grad_scale=None):
         # written on the engine's stream: the kernels that read hp (SGD, fused combines) run
         # there, so the write is ordered before the next step and after the previous one
+        if momentum is not None and self.opt.name != "sgd":
+            raise ValueError("momentum is an SGD hyper-parameter (slot 1 holds Adam's beta1)")
         with self._on_stream(), torch.no_grad():
             # fill_ with a scalar is a kernel launch (capturable inside a graph, e.g. the
             # per-step scales of run_epoch); item assignment would copy a host tensor
@@ -416,6 +445,10 @@ class MLPEngine:
         return self._BODIES[self._schedule()[0]][1]
 
     def _step_body(self, first: bool):
+        # Adam: the device step number advances and the bias corrections are refreshed first, on
+        # the compute stream -- behind the previous step's join, ahead of every update of this
+        # step on either stream (they wait for events recorded after it).  SGD launches nothing.
+        self.opt.tick()
         self._mark("start")
         body = self._schedule()[0]
         if not body.startswith("rowband"):
@@ -443,8 +476,7 @@ class MLPEngine:
             self.sync.launch_bucket(b, self.stream)
         self.sync.finish()
         self._mark("comm")
-        kw = {} if images is None else {"images": images}
-        self.ops.sgd(self.arena, self.hp, self.nesterov, first, zero_grad=zero_grad, **kw)
+        self.opt.apply(first, zero_grad=zero_grad, images=images)
         if images is not None:
             self.images.mark(True)
 
@@ -546,10 +578,10 @@ class MLPEngine:
         self._sgd_layers(unfused, first)
 
     def _sgd_layers(self, layers, first: bool):
-        """Separate SGD passes for the layers whose kernels could not apply the update."""
+        """Separate optimizer passes for the layers whose kernels could not apply the update."""
         for i in layers:
             s, e = self.arena.layer_range[i]
-            self.ops.sgd(self.arena, self.hp, self.nesterov, first, offset=s, numel=e - s)
+            self.opt.apply(first, offset=s, numel=e - s)
 
     def check_device_errors(self):
         """Raise if a column-split row-band step gave up a bounded wait (a band's blocks were not
@@ -720,11 +752,11 @@ class MLPEngine:
                               file=sys.stderr, flush=True)
                         self.use_graph = False
                         self._step_body(False)
-                        self.steps_done += 1
+                        self._steps += 1
                         return
                     self._graphs[key] = g
                 g.launch(int(self.stream.cuda_stream))
-        self.steps_done += 1
+        self._steps += 1
 
     # ---------------- multi-step graphs ------------------------------------------------------
     # A hipGraph replay has a fixed cost (~8 us measured between consecutive replays on MI355X,
@@ -783,7 +815,7 @@ class MLPEngine:
                     int(self.stream.cuda_stream))
                 if hist:
                     losses[k0:k0 + c].copy_(self._loss_hist[:c])
-                self.steps_done += c
+                self._steps += c
                 k0 += c
 
     def run_epoch(self, X: torch.Tensor, Y: Optional[torch.Tensor],
@@ -817,7 +849,7 @@ class MLPEngine:
                 self.rows = hi - lo
                 self.inv_count, self.loss_scale = float(inv), float(lsc)
             g.launch(int(self.stream.cuda_stream))
-        self.steps_done += len(plan)
+        self._steps += len(plan)
 
     def _capture(self, nsteps: int = 1, hist: bool = False):
         """One graph of ``nsteps`` consecutive steps; ``hist``: step k also copies its loss into
@@ -907,6 +939,7 @@ class MLPEngine:
         first = self.steps_done == 0
         ar = self.arena
         with self._on_stream(), torch.no_grad():
+            self.opt.tick()      # once per optimizer step, however many micro-batches it summed
             ar.grad.copy_(self._acc)
             self.loss_out[:1].copy_(self._acc_loss)
             self._first = first
@@ -917,7 +950,7 @@ class MLPEngine:
             self.pipe.update_all(first)
         self.images.mark(False)
         self._n_acc = 0
-        self.steps_done += 1
+        self._steps += 1
 
     # ---------------- evaluation (forward only) ---------------------------------------------
     def evaluate(self, X: torch.Tensor, Y: Optional[torch.Tensor] = None,

@@ -18,16 +18,19 @@ from typing import Dict, List, Optional, Tuple
 
 import torch
 from ..utils.knobs import knob
+from .optimizer import Sgd
 
 
 class BucketPipeline:
     def __init__(self, spec, arena, ops, sync, hp, nesterov: bool, stream, *, grad16, bf16: bool,
-                 defer: bool):
+                 defer: bool, opt=None):
         """``grad16``: the bf16 payload the per-bucket updates read (None: the fp32 gradient);
         ``bf16``: bf16 compute; ``defer``: the schedule launches the chunk weight gradients that
-        can carry deferred updates."""
+        can carry deferred updates; ``opt``: the optimizer every update goes through
+        (engine/optimizer.py; default: SGD-momentum over ``hp``)."""
         self.spec, self.arena, self.ops, self.sync = spec, arena, ops, sync
         self.hp, self.nesterov, self.stream = hp, nesterov, stream
+        self.opt = opt if opt is not None else Sgd(ops, arena, hp, nesterov)
         self.sharded = sync.sharded
         # ev_wfree[l]: the last reader of layer l's weights has been issued
         self.ev_wfree = ([torch.cuda.Event(enable_timing=False) for _ in range(spec.n_layers)]
@@ -45,7 +48,9 @@ class BucketPipeline:
         # (not for the row-band schedules: they never launch the chunk weight gradients whose
         # epilogues would apply these updates, so every target bucket would fall to join())
         self.defer_plan: Dict[int, object] = {}
-        if self.w16 and defer and not self.sharded and knob("NNMPI_DEFER", "1") != "0":
+        # (only an optimizer the epilogues can apply: linear_wgrad_defer runs sgd_elem)
+        if (self.w16 and defer and not self.sharded and self.opt.fusable
+                and knob("NNMPI_DEFER", "1") != "0"):
             for i in range(spec.n_layers - 2):
                 if spec.layer_shape(i) != spec.layer_shape(i + 1):
                     continue
@@ -80,15 +85,14 @@ class BucketPipeline:
         self._reset(first, images)
 
     def sgd(self, offset: int, numel: int):
-        self.ops.sgd(self.arena, self.hp, self.nesterov, self.first, offset=offset, numel=numel,
-                     **self.upd_kw)
+        self.opt.apply(self.first, offset=offset, numel=numel, **self.upd_kw)
 
     def update_all(self, first: bool):
         """Optimizer update of the whole arena (or, sharded, of this rank's slice + gathers)."""
         if self.sharded:
-            self.sync.update(self.ops, self.hp, self.nesterov, first)
+            self.sync.update(self.ops, self.hp, self.nesterov, first, opt=self.opt)
         else:
-            self.ops.sgd(self.arena, self.hp, self.nesterov, first)
+            self.opt.apply(first)
 
     def bucket_reduce(self, b, stream):
         """Launch bucket b's collective (once); returns the stream it completes on.  One queued

@@ -8,7 +8,8 @@ Per rank:
   3. initialise the model on rank 0 with ``torch.manual_seed(0)`` (ref.py:69,84) and broadcast it
      (ref.py:87-88) into the flat arena that backs the model's parameters;
   4. run the epoch loop: one optimizer step per batch (full shard by default, ref.py:146),
-     gradients synchronised by bucketed all-reduce, fused SGD-momentum; print the reference's
+     gradients synchronised by bucketed all-reduce, fused SGD-momentum (or ``--optimizer adam``
+     / ``adamw``: one Adam pass of the same shape); print the reference's
      two log lines (ref.py:152,224);
   5. optionally checkpoint (reference-format state_dict) / resume, emit JSON metrics.
 """
@@ -304,10 +305,11 @@ def loss_scales(cfg: TrainConfig, rows_local: int, rows_all: List[int], out_f: i
 
 
 def _gather_state(eng, sync):
-    """Sharded optimizer: re-assemble the full fp32 master + momentum on every rank (collective)."""
+    """Sharded optimizer: re-assemble the full fp32 master + optimizer state on every rank
+    (collective)."""
     if sync.sharded:
         eng.synchronize()
-        sync.gather_state()
+        sync.gather_state(eng.opt.state_buffers())
 
 
 def _comm_only_ms(j: "Job", sync, reps: int = 10) -> float:
@@ -395,7 +397,7 @@ def _run(j: Job) -> TrainResult:
     broadcast_params(j, arena)
     start_epoch, steps_done = 0, 0
     if cfg.resume:
-        start_epoch, steps_done = ckpt.load_training_state(cfg.resume, arena)
+        start_epoch, steps_done = ckpt.load_training_state(cfg.resume, arena, cfg.optimizer)
     sync = make_sync(j, arena)
     ops = make_ops(j)
     bs = cfg.batch_size
@@ -409,8 +411,9 @@ def _run(j: Job) -> TrainResult:
                     rowband_overlap=cfg.comm_mode == "overlap_rowband",
                     rows_capacity=max(cap, 1), lr=cfg.lr, momentum=cfg.momentum,
                     dampening=cfg.dampening, weight_decay=cfg.weight_decay,
-                    nesterov=cfg.nesterov, use_graph=cfg.graph, overlap=cfg.overlap)
-    eng.steps_done = steps_done
+                    nesterov=cfg.nesterov, use_graph=cfg.graph, overlap=cfg.overlap,
+                    optimizer=cfg.optimizer, beta1=cfg.beta1, beta2=cfg.beta2, eps=cfg.eps)
+    eng.steps_done = steps_done      # (also the optimizer's device-side step number)
     if cfg.profile_steps:
         from ..utils.metrics import EventTimer
         eng.timer = EventTimer(j.device.type)
@@ -428,7 +431,7 @@ def _run(j: Job) -> TrainResult:
                     "grad_dtype": grad_payload(cfg, j.device.type, arena.numel),
                     "inline": bool(getattr(sync, "inline", False)),
                     "grouped": bool(eng.grouped), "rowband": eng.uses_rowband(rows_local),
-                    "deferred_updates": len(eng._defer_plan),
+                    "deferred_updates": len(eng._defer_plan), "optimizer": eng.opt.name,
                     "graph": bool(eng.use_graph)}
     n_micro = max(1, math.ceil(max_rows / mb)) if mb else 1
     steps_per_epoch = math.ceil(n_micro / K) if K > 1 else (1 if not bs else n_micro)

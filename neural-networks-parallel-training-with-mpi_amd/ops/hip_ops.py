@@ -450,6 +450,54 @@ class HipOps(OpSet):
         self.lib.gather_rows(_p(src), _p(dst), _p(idx), n, row_bytes, src.shape[0], self.stream)
 
     # ---------------- optimizer ----------------
+    @staticmethod
+    def _image_pack(arena, images, offset: int, n: int):
+        """The (start, M, N, pkf, pkd) entries of the row-band images whose weights lie (partly)
+        inside the pass over [offset, offset + n); None without images."""
+        if not images:
+            return None
+        pack = []
+        for li, (pf, pd) in images.items():
+            slot = arena.by_name[f"layers.{2 * li}.weight"]
+            M, N = slot.shape
+            if slot.offset < offset + n and slot.offset + M * N > offset:
+                pack.append((slot.offset - offset, M, N, _p(pf), _p(pd) if pd is not None else 0))
+        return pack
+
+    def adam_tick(self, hp, t):
+        """Advance the device step counter ``t`` (int32) and refresh the bias corrections in
+        ``hp`` (one single-thread launch: capturable, so a replayed graph counts its steps)."""
+        _check(t.dtype == torch.int32 and t.numel() >= 1 and hp.dtype == torch.float32 and
+               hp.numel() >= int(self.lib.ADAM_HP_LEN), "adam_tick: int32 counter, 12-slot fp32 hp")
+        self.lib.adam_tick(_p(hp), _p(t), self.stream)
+
+    def adam(self, arena, hp, t, decoupled: bool, zero_grad: bool = True, offset: int = 0,
+             numel: int = None, grad_bf16=None, images=None):
+        """Adam (``decoupled``: AdamW) over ``[offset, offset + numel)`` of the arena, mirroring
+        :meth:`sgd`: exp_avg is ``arena.momentum``, exp_avg_sq ``arena.exp_avg_sq``.  ``t`` is
+        not read by the pass -- the bias corrections adam_tick left in ``hp`` are -- and is taken
+        so both op sets share one signature."""
+        n = arena.numel - offset if numel is None else numel
+        _check(arena.exp_avg_sq is not None, "adam: the arena has no exp_avg_sq buffer "
+                                             "(Arena.ensure_exp_avg_sq)")
+        _check(n % 4 == 0 and offset % 4 == 0, f"adam: offset and numel % 4 == 0 ({offset}, {n})")
+        _check(0 <= offset and 0 <= n and offset + n <= arena.numel, "adam: range outside the arena")
+        _check(hp.dtype == torch.float32 and hp.numel() >= int(self.lib.ADAM_HP_LEN),
+               "adam: the 12-slot Adam hyper-parameter tensor")
+        e = 4  # bytes per fp32 element
+        sh = _p(arena.shadow) + 2 * offset if arena.shadow is not None else 0
+        pack = self._image_pack(arena, images, offset, n)
+        args = (_p(arena.momentum) + e * offset, _p(arena.exp_avg_sq) + e * offset, sh, n, _p(hp),
+                int(bool(decoupled)))
+        if grad_bf16 is not None:
+            _check(grad_bf16.dtype == torch.bfloat16 and grad_bf16.numel() >= offset + n,
+                   "adam: bf16 gradient buffer too small")
+            self.lib.adam_update_bf16grad(_p(arena.master) + e * offset, _p(grad_bf16) + 2 * offset,
+                                          *args, self.stream, pack)
+            return
+        self.lib.adam_update(_p(arena.master) + e * offset, _p(arena.grad) + e * offset, *args,
+                             int(zero_grad), self.stream, pack)
+
     def sgd(self, arena, hp, nesterov: bool, first: bool, zero_grad: bool = True, offset: int = 0,
             numel: int = None, grad_bf16=None, images=None):
         """``grad_bf16``: read the gradient from this bf16 buffer (same layout as the arena)
@@ -459,14 +507,7 @@ class HipOps(OpSet):
         n = arena.numel - offset if numel is None else numel
         e = 4  # bytes per fp32 element
         sh = _p(arena.shadow) + 2 * offset if arena.shadow is not None else 0
-        pack = None
-        if images:
-            pack = []
-            for li, (pf, pd) in images.items():
-                slot = arena.by_name[f"layers.{2 * li}.weight"]
-                M, N = slot.shape
-                if slot.offset < offset + n and slot.offset + M * N > offset:
-                    pack.append((slot.offset - offset, M, N, _p(pf), _p(pd) if pd is not None else 0))
+        pack = self._image_pack(arena, images, offset, n)
         if grad_bf16 is not None:
             _check(grad_bf16.dtype == torch.bfloat16 and grad_bf16.numel() >= offset + n,
                    "sgd: bf16 gradient buffer too small")

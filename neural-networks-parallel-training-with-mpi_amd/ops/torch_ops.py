@@ -109,3 +109,43 @@ class TorchOps(OpSet):
                 arena.shadow[sl].copy_(p)
             if zero_grad:
                 g.zero_()
+
+    # ---- Adam / AdamW: hp in the Adam layout (engine/optimizer.py ADAM_*, optim.hip) ----------
+    def adam_tick(self, hp, t):
+        """t += 1 (int32 tensor of one element); hp[6], hp[7] = 1 - beta1^t, 1 - beta2^t, computed
+        in double from the betas the host stored (slot + remainder slot) -- as adam_tick_kernel."""
+        with torch.no_grad():
+            t.add_(1)
+            step = int(t.item())
+            h = hp.tolist()
+            b1, b2 = h[1] + h[10], h[2] + h[11]
+            hp[6:8].copy_(torch.tensor([1.0 - b1 ** step, 1.0 - b2 ** step], dtype=torch.float32))
+
+    def adam(self, arena, hp, t, decoupled: bool, zero_grad: bool = True, offset: int = 0,
+             numel: int = None, grad_bf16=None, images=None):
+        """The update of adam_kernel in plain torch: the same operations in fp32, in its order
+        (``t`` is not read: the bias corrections come from ``hp``, as in the kernel)."""
+        if images:
+            raise ValueError("TorchOps.adam: the row-band weight images are a HIP path")
+        f32 = lambda x: torch.tensor(x, dtype=torch.float32, device=hp.device)  # noqa: E731
+        h = hp.detach()
+        lr, b1, b2, wd, gs, eps, bc1, bc2, omb1, omb2 = [h[k] for k in range(10)]
+        n = arena.numel - offset if numel is None else numel
+        sl = slice(offset, offset + n)
+        p, g, m, v = arena.master[sl], arena.grad[sl], arena.exp_avg[sl], arena.exp_avg_sq[sl]
+        if grad_bf16 is not None:
+            g = grad_bf16[sl].float()
+            zero_grad = False
+        with torch.no_grad():
+            d = g * gs
+            if decoupled:
+                p.mul_(f32(1.0) - lr * wd)
+            elif float(wd) != 0:
+                d = d + wd * p
+            m.mul_(b1).add_(omb1 * d)
+            v.mul_(b2).add_((omb2 * d) * d)
+            p.sub_((lr / bc1) * (m / (v.sqrt() / bc2.sqrt() + eps)))
+            if arena.shadow is not None:
+                arena.shadow[sl].copy_(p)
+            if zero_grad:
+                g.zero_()

@@ -384,10 +384,19 @@ class ShardedSync(GradSync):
         self.off = rank * self.shard
         self.comm = native_comm
         self.group = group
+        # NNMPI_F32_REDUCE=ordered (RCCL path): the reduce-scatter sums every element in rank
+        # order, as the ordered all-reduce does (RcclComm::reduce_scatter_f32_ordered), so at
+        # P >= 3 a ZeRO-1 run agrees bit for bit with an all-reduce run under the same knob
+        # (ncclReduceScatter's ring sums slice r in the order r+1, ..., r).  Default: rccl.
+        self.scratch32 = None
         if native_comm is not None:
             from .. import native
             self.native = native
+            if knob("NNMPI_F32_REDUCE", "rccl") == "ordered" and world > 1:
+                self.scratch32 = torch.empty(arena.numel, dtype=torch.float32,
+                                             device=arena.grad.device)
         self.pieces = self._master_pieces()
+        self._opt = None   # the optimizer object of the last update()
 
     def _master_pieces(self):
         """(offsets, counts, roots) of the fp32-master regions the kernels read besides the
@@ -419,17 +428,29 @@ class ShardedSync(GradSync):
     def _views(self, buf):
         return [buf[r * self.shard:(r + 1) * self.shard] for r in range(self.world)]
 
-    def update(self, ops, hp, nesterov: bool, first: bool):
-        """Reduce-scatter -> owner SGD -> all-gather, on the current (compute) stream."""
+    def _reduce_scatter(self, h: int):
+        g = self.arena.grad.data_ptr()
+        if self.scratch32 is not None:
+            self.comm.reduce_scatter_f32_ordered(g, self.scratch32.data_ptr(), self.shard, h)
+        else:
+            self.comm.reduce_scatter(g, g + 4 * self.off, self.shard, 0, 0, h)
+
+    def update(self, ops, hp, nesterov: bool, first: bool, opt=None):
+        """Reduce-scatter -> owner update -> all-gather, on the current (compute) stream.
+        ``opt``: the optimizer object (engine/optimizer.py) applied to the owner slice; default
+        SGD-momentum over ``hp``."""
         ar = self.arena
+        if opt is None:
+            from ..engine.optimizer import Sgd
+            opt = Sgd(ops, ar, hp, nesterov)
+        self._opt = opt
         self.note(3, 0, 0, self.shard, 0)
         if self.comm is not None:
             h = self.native.stream_handle()
-            g = ar.grad.data_ptr()
-            self.comm.reduce_scatter(g, g + 4 * self.off, self.shard, 0, 0, h)
+            self._reduce_scatter(h)
         else:
             dist.all_reduce(ar.grad, group=self.group)
-        ops.sgd(ar, hp, nesterov, first, offset=self.off, numel=self.shard)
+        opt.apply(first, offset=self.off, numel=self.shard)
         if self.comm is not None:
             if ar.shadow is not None:
                 s = ar.shadow.data_ptr()
@@ -453,8 +474,7 @@ class ShardedSync(GradSync):
                             ar.master[self.off:self.off + self.shard].clone(), group=self.group)
             return
         h = self.native.stream_handle()
-        g = ar.grad.data_ptr()
-        self.comm.reduce_scatter(g, g + 4 * self.off, self.shard, 0, 0, h)
+        self._reduce_scatter(h)
         if ar.shadow is not None:
             s = ar.shadow.data_ptr()
             self.comm.allgather(s + 2 * self.off, s, self.shard, 1, h)
@@ -464,10 +484,14 @@ class ShardedSync(GradSync):
             m = ar.master.data_ptr()
             self.comm.allgather(m + 4 * self.off, m, self.shard, 0, h)
 
-    def gather_state(self):
-        """Full fp32 master + momentum on every rank (checkpoint / final parameters)."""
+    def gather_state(self, state_buffers=None):
+        """Full fp32 master + every optimizer state buffer on every rank (checkpoint / final
+        parameters).  ``state_buffers``: the optimizer's ``state_buffers()`` (SGD: momentum; Adam:
+        exp_avg and exp_avg_sq); default: those of the optimizer the last update() applied."""
         ar = self.arena
-        for buf in (ar.master, ar.momentum):
+        if state_buffers is None:
+            state_buffers = self._opt.state_buffers() if self._opt is not None else [ar.momentum]
+        for buf in [ar.master] + list(state_buffers):
             own = buf[self.off:self.off + self.shard]
             if self.comm is not None:
                 import torch as _t

@@ -52,6 +52,11 @@ class TrainConfig:
     dampening: float = 0.0
     weight_decay: float = 0.0
     nesterov: bool = False
+    # --- optimizer choice (torch.optim.Adam / AdamW semantics; momentum is ignored under them) ---
+    optimizer: str = "sgd"            # sgd | adam | adamw
+    beta1: float = 0.9
+    beta2: float = 0.999
+    eps: float = 1e-8
     # --- data ---
     n_samples: int = 16
     n_features: Optional[int] = None  # defaults to widths[0]
@@ -132,6 +137,13 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--dampening", type=float, default=0.0)
     p.add_argument("--weight_decay", type=float, default=0.0)
     p.add_argument("--nesterov", action="store_true")
+    p.add_argument("--optimizer", choices=["sgd", "adam", "adamw"], default="sgd",
+                   help="sgd: SGD-momentum (the reference's); adam / adamw: torch.optim.Adam / "
+                        "AdamW semantics (--weight_decay is L2 under adam, decoupled under adamw; "
+                        "--momentum is ignored)")
+    p.add_argument("--beta1", type=float, default=0.9, help="Adam beta1 [0.9]")
+    p.add_argument("--beta2", type=float, default=0.999, help="Adam beta2 [0.999]")
+    p.add_argument("--eps", type=float, default=1e-8, help="Adam eps [1e-8]")
     p.add_argument("--n_samples", type=int, default=None)
     p.add_argument("--n_features", type=int, default=None)
     p.add_argument("--noise", type=float, default=1.0)
@@ -259,6 +271,14 @@ def validate(cfg: TrainConfig) -> None:
         raise ValueError(cfg.dtype)
     if cfg.nesterov and (cfg.momentum <= 0 or cfg.dampening != 0):
         raise ValueError("Nesterov momentum requires a momentum and zero dampening")
+    if cfg.optimizer not in ("sgd", "adam", "adamw"):
+        raise ValueError(f"optimizer must be sgd, adam or adamw, got {cfg.optimizer!r}")
+    if not (0.0 <= cfg.beta1 < 1.0 and 0.0 <= cfg.beta2 < 1.0):
+        raise ValueError(f"beta1 and beta2 must be in [0, 1), got {cfg.beta1}, {cfg.beta2}")
+    if not cfg.eps > 0:
+        raise ValueError(f"eps must be > 0, got {cfg.eps}")
+    if cfg.optimizer != "sgd" and (cfg.nesterov or cfg.dampening != 0):
+        raise ValueError(f"--nesterov / --dampening are SGD options, not for {cfg.optimizer}")
     if cfg.lr < 0 or cfg.momentum < 0 or cfg.weight_decay < 0:
         raise ValueError("lr, momentum and weight_decay must be >= 0")
     if cfg.batch_size is not None and cfg.batch_size <= 0:
