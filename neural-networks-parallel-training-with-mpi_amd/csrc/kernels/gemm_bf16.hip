@@ -512,8 +512,30 @@ int gemm_host::pick_tile(int M, int N) {
   return t128 >= 192 ? 128 : 64;
 }
 
+// The operands the loaders take (docs/ARCHITECTURE.md §5 has the table).  Both main loops move
+// 16-byte chunks of 8 bf16 -- the DMA ring as buffer loads into LDS, the register-staged loop as
+// uint4 loads -- so every chunk must start on a 16-byte boundary (base aligned, ld % 8 == 0), and
+// a KMAJ operand, whose chunks run along k, needs K % 8 == 0 (a chunk across the end of K would
+// carry the next row's head into the sum).  The DMA plan's byte offsets are 32-bit, checked
+// against a buffer range that set_extents caps at DMA_OOB - 16: of a larger operand the part
+// beyond the cap would read as zeros.  Refused here, before anything is launched.
+static bool operand_ok(const bf16* P, int ld, int layout, int X, int K) {
+  if (P == nullptr || ((uintptr_t)P & 15) != 0 || ld <= 0 || ld % 8 != 0) return false;
+  if (layout == KMAJ && K % 8 != 0) return false;
+  // an XMAJ chunk across the end of X feeds only rows or columns that are never stored; the DMA
+  // range check clips it at the end of the storage, the register-staged loop's plain load does not
+  if (layout == XMAJ && X % 8 != 0 && gemm_impl() != 2) return false;
+  const long long ext = (layout == KMAJ) ? ((long long)(X - 1) * ld + K) : ((long long)(K - 1) * ld + X);
+  return ext * 2 <= (long long)DMA_OOB - 16;
+}
+static bool operands_ok(const bf16* A, int lda, int la, const bf16* B, int ldb, int lb, int M, int N,
+                        int K) {
+  return operand_ok(A, lda, la, M, K) && operand_ok(B, ldb, lb, N, K);
+}
+
 hipError_t linear_fwd_bf16(const bf16* X, int ldx, const bf16* W, int ldw, const float* bias,
                            bf16* Y, int ldy, int M, int N, int K, int act, hipStream_t s) {
+  if (!operands_ok(X, ldx, KMAJ, W, ldw, KMAJ, M, N, K)) return hipErrorInvalidValue;
   GemmParams p{};
   p.A = X; p.lda = ldx; p.B = W; p.ldb = ldw; p.M = M; p.N = N; p.K = K;
   p.k_per_split = ((K + GEMM_BK - 1) / GEMM_BK) * GEMM_BK;
@@ -531,6 +553,7 @@ hipError_t linear_fwd_bf16(const bf16* X, int ldx, const bf16* W, int ldw, const
 hipError_t linear_dgrad_bf16(const bf16* dZ, int lddz, const bf16* W, int ldw, const bf16* Aprev,
                              int lda_prev, bf16* dX, int lddx, int M, int N, int K, int act,
                              hipStream_t s) {
+  if (!operands_ok(dZ, lddz, KMAJ, W, ldw, XMAJ, M, N, K)) return hipErrorInvalidValue;
   GemmParams p{};
   p.A = dZ; p.lda = lddz; p.B = W; p.ldb = ldw; p.M = M; p.N = N; p.K = K;
   p.k_per_split = ((K + GEMM_BK - 1) / GEMM_BK) * GEMM_BK;
@@ -610,6 +633,7 @@ hipError_t linear_wgrad_bf16_deferred(const bf16* dZ, int lddz, const bf16* X, i
 hipError_t linear_wgrad_bf16_ex(const bf16* dZ, int lddz, const bf16* X, int ldx, float* dW,
                                 float* db, int M, int N, int K, float* ws, hipStream_t s,
                                 const SgdFuse* sgd, SlabReduce* pending, bf16* dW16, bf16* db16) {
+  if (!operands_ok(dZ, lddz, XMAJ, X, ldx, XMAJ, M, N, K)) return hipErrorInvalidValue;
   WgradArgs a{dZ, lddz, X, ldx, dW, db, M, N, K, ws, SgdFuse{}, dW16, db16};
   if (sgd) a.sg = *sgd;
   if (dW16 && (sgd || wgrad_splits(M, N, K) > 1)) return hipErrorInvalidValue;
@@ -643,6 +667,7 @@ hipError_t linear_wgrad_bf16_out16_defer(const bf16* dZ, int lddz, const bf16* X
                                          bf16* db16, int M, int N, int K, const SgdFuse& other,
                                          const bf16* g16o, hipStream_t s) {
   if (!wgrad_defer_ok(M, N, K) || !dW16 || !db16 || !g16o || !other.p_base) return hipErrorInvalidValue;
+  if (!operands_ok(dZ, lddz, XMAJ, X, ldx, XMAJ, M, N, K)) return hipErrorInvalidValue;
   WgradArgs a{dZ, lddz, X, ldx, nullptr, nullptr, M, N, K, nullptr, SgdFuse{}, dW16, db16};
   GemmParams p;
   SlabReduce r;
@@ -666,6 +691,7 @@ hipError_t gemm_bf16_generic_tile(const bf16* A, int lda, int la, const bf16* B,
   // The same plain GEMM through the 256x256 ping-pong kernel (tile 256) or the 128x128 DMA
   // kernel (tile 128): operand-layout experiments on the production tiles.
   if (tile != 256 && tile != 128) return gemm_bf16_generic(A, lda, la, B, ldb, lb, M, N, K, C, ldc, s);
+  if (!operands_ok(A, lda, la, B, ldb, lb, M, N, K)) return hipErrorInvalidValue;
   GemmParams p{};
   p.A = A; p.lda = lda; p.B = B; p.ldb = ldb; p.M = M; p.N = N; p.K = K;
   p.k_per_split = ((K + GEMM_BK - 1) / GEMM_BK) * GEMM_BK;
@@ -683,6 +709,7 @@ hipError_t gemm_bf16_generic_tile(const bf16* A, int lda, int la, const bf16* B,
 hipError_t gemm_bf16_generic(const bf16* A, int lda, int la, const bf16* B, int ldb, int lb,
                              int M, int N, int K, float* C, int ldc, hipStream_t s) {
   // Plain fp32-output GEMM in any of the four layout combinations (testing / utility).
+  if (!operands_ok(A, lda, la, B, ldb, lb, M, N, K)) return hipErrorInvalidValue;
   GemmParams p{};
   p.A = A; p.lda = lda; p.B = B; p.ldb = ldb; p.M = M; p.N = N; p.K = K;
   p.k_per_split = ((K + GEMM_BK - 1) / GEMM_BK) * GEMM_BK;
@@ -764,6 +791,10 @@ bool bwd_group_supported(int rows, int out_f, int in_f) {
 hipError_t bwd_group(const DgradArgs* dg, const WgradArgs* wg, const SlabReduce* red,
                      SlabReduce* wg_pending, hipStream_t s) {
   if (wg_pending) *wg_pending = SlabReduce{};
+  if (dg && !operands_ok(dg->dZ, dg->lddz, KMAJ, dg->W, dg->ldw, XMAJ, dg->M, dg->N, dg->K))
+    return hipErrorInvalidValue;
+  if (wg && !operands_ok(wg->dZ, wg->lddz, XMAJ, wg->X, wg->ldx, XMAJ, wg->M, wg->N, wg->K))
+    return hipErrorInvalidValue;
   int nb_main = 0, nb_bias = 0, nbr = 0;
   if (red) slab_blocks(*red, nb_main, nb_bias, nbr);
   GemmParams pw{};

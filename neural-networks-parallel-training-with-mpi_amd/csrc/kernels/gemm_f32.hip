@@ -184,14 +184,14 @@ hipError_t linear_wgrad_f32(const float* dZ, int lddz, const float* X, int ldx, 
     return db ? f32g::launch<f32g::XMAJ, f32g::XMAJ, EPI_F32, true>(p, 0, 1, s)
               : f32g::launch<f32g::XMAJ, f32g::XMAJ, EPI_F32, false>(p, 0, 1, s);
   }
-  if (!ws) return hipErrorInvalidValue;
+  // (the combine moves float4 columns: refuse before the GEMM has run into the workspace)
+  if (!ws || N % 4 != 0) return hipErrorInvalidValue;
   p.C = ws; p.ldc = N; p.c_split_stride = (long long)M * N;
   float* bws = ws + (size_t)splits * M * N;
   p.bias_grad = bws; p.bg_split_stride = M;
   hipError_t e = db ? f32g::launch<f32g::XMAJ, f32g::XMAJ, EPI_F32, true>(p, 0, splits, s)
                     : f32g::launch<f32g::XMAJ, f32g::XMAJ, EPI_F32, false>(p, 0, splits, s);
   if (e != hipSuccess) return e;
-  if (N % 4 != 0) return hipErrorInvalidValue;
   return splitk_reduce(ws, splits, (long long)M * N, M, N, dW, N, db ? bws : nullptr, M, db,
                        nullptr, 0, 0.f, nullptr, s);
 }
