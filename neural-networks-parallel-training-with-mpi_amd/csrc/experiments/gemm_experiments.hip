@@ -7,8 +7,8 @@
 //                                     (NNMPI_PAIR=1): 0.6 % slower on the wide step;
 //   * gemm_bf16_dma_stamp_kernel   -- per-block entry/exit stamps of the 128x128 forward
 //                                     (scripts/stamp_fwd.py).
-// The production file reaches them through the weak references declared in gemm_tiles.h.
-#include "kernels/gemm_tiles.h"
+// The production file reaches them through the weak references declared in gemm_host.h.
+#include "kernels/gemm_host.h"
 #include "knobs.h"
 
 namespace nnmpi {

@@ -22,7 +22,7 @@
 // bank model).  Blocks are remapped so consecutive tiles share an XCD (T1).  The wgrad bias
 // gradient (row sums of dZ^T) rides on the same A fragments through one extra MFMA against a
 // ones operand in the n-tile-0 blocks.
-#include "gemm_tiles.h"
+#include "gemm_host.h"
 #include "knobs.h"
 
 namespace nnmpi {
@@ -254,6 +254,14 @@ __device__ __forceinline__ void slab_reduce_deep_block(const SlabReduce& r, int 
 
 constexpr int SLAB_PART_BYTES = 16 * 64 * 16;   // max(WS, NW) x 64 lanes x f32x4
 
+// Virtual-wave count for S <= 64 partial slabs: ~8 independent loads per lane, WS = S / 8
+// rounded up to a power of two, in [1, 16] (host: slab_ws; device: the in-launch fixup)
+__host__ __device__ __forceinline__ int slab_ws_n(int S) {
+  int ws = 1;
+  while (ws < 16 && ws * 8 < S) ws *= 2;
+  return ws;
+}
+
 template <int WS>
 __global__ void __launch_bounds__(SLAB_THREADS) slab_reduce_kernel(SlabReduce r, int nb_main, int nb_bias) {
   __shared__ f32x4 part[SLAB_PART_BYTES / 16];
@@ -284,10 +292,6 @@ struct BwdGroupParams {
   SlabReduce red;
   int red_ws, nb_main, nb_bias;
 };
-
-constexpr int GRP_BM = 128, GRP_BN = 128, GRP_WGM = 2, GRP_WGN = 4, GRP_NS = 2;
-constexpr int GRP_THREADS = 64 * GRP_WGM * GRP_WGN;
-constexpr int GRP_SMEM = GRP_NS * (GRP_BM + GRP_BN) * GEMM_BK * 2;
 
 // GA: LDS read mode of the two GEMM jobs (dma_gemm_tile ASYNC_TR).  Two 64 KiB / 512-thread
 // blocks per CU (4 waves per SIMD) is what lets one block's DMA wait hide behind the other's
@@ -722,11 +726,7 @@ hipError_t gemm_bf16_generic(const bf16* A, int lda, int la, const bf16* B, int 
 
 static int slab_ws(const SlabReduce& r) {
   // more than 64 partials: the deep 16-column form
-  if (r.S > 64) return SLAB_DEEP;
-  // ~8 independent loads per lane: WS = S / 8 rounded up to a power of two, in [1, 16]
-  int ws = 1;
-  while (ws < 16 && ws * 8 < r.S) ws *= 2;
-  return ws;
+  return r.S > 64 ? SLAB_DEEP : slab_ws_n(r.S);
 }
 
 static int slab_cols(int ws) {
@@ -1066,12 +1066,6 @@ __device__ __forceinline__ void wg_reg_tile(const GemmParams& p, char* smem, int
 //     the bias rows of the portion.
 // The counters and claim words (WGM_CW per tile) are zeroed by the row-band launch before every
 // weight-gradient launch (RowbandArgs::zero_words).
-// slab_multi's virtual-wave count for S partial slabs (slab_ws, S <= 64)
-__host__ __device__ __forceinline__ int slab_ws_n(int S) {
-  int ws = 1;
-  while (ws < 16 && ws * 8 < S) ws *= 2;
-  return ws;
-}
 constexpr int WGM_MAXS = 16;       // most splits the fixup takes (more: the combine launch)
 constexpr int WGM_CW = 32;         // counter words per tile: [0] arrivals, [1 + p] portion claims
 constexpr int WGM_SPIN = 400;      // polls of an early split (x ~0.2 us) before it gives up
@@ -1380,13 +1374,7 @@ static hipError_t wgm_launch(const WgradMultiParams& g, int nb, bool fix, hipStr
   else f = ga == 2 ? wgm_fn<2, 2>(fix, st) : ga == 3 ? wgm_fn<3, 2>(fix, st) : wgm_fn<4, 2>(fix, st);
   if (!f) return hipErrorNotSupported;
   const int smem = (ns == 0 ? 2 : ns) * (GRP_BM + GRP_BN) * GEMM_BK * 2;
-  static void* attr_done[64] = {};
-  bool seen = false;
-  for (void*& a : attr_done) {
-    if (a == f) { seen = true; break; }
-    if (!a) { a = f; break; }
-  }
-  if (!seen) (void)hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, smem);
+  dyn_lds_once(f, smem);
   hipLaunchKernelGGL(reinterpret_cast<void (*)(WgradMultiParams)>(f), dim3(nb), dim3(GRP_THREADS), smem, s, g);
   return hipGetLastError();
 }
@@ -1446,13 +1434,7 @@ hipError_t wgrad_multi(const WgradArgs* jobs, int nj, const int* splits, SlabRed
     const int ga = env_ga == 3 ? 3 : env_ga == 4 ? 4 : 2;
     void* f = ga == 3 ? (void*)wgrad_multi_h_kernel<3> : ga == 4 ? (void*)wgrad_multi_h_kernel<4>
                                                                : (void*)wgrad_multi_h_kernel<2>;
-    static void* attr_done[4] = {};
-    bool seen = false;
-    for (void*& a : attr_done) {
-      if (a == f) { seen = true; break; }
-      if (!a) { a = f; break; }
-    }
-    if (!seen) (void)hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, WGH_SMEM);
+    dyn_lds_once(f, WGH_SMEM);
     hipLaunchKernelGGL(reinterpret_cast<void (*)(WgradMultiParams)>(f), dim3(nb), dim3(WGH_THREADS),
                        WGH_SMEM, s, g);
     return hipGetLastError();

@@ -1,8 +1,9 @@
-// Device-side building blocks of the bf16 MFMA GEMMs (gemm_bf16.hip): operand layouts, LDS
-// images, the LDS-DMA plan, the 128x128 DMA main loop and the 256x256 ping-pong tile with their
-// fused epilogues.  Shared by the production launchers (gemm_bf16.hip) and the experiment
-// kernels (csrc/experiments/, built only with NNMPI_BUILD_EXPERIMENTS=1).  See gemm_bf16.hip for the
-// design notes.
+// Device-side building blocks of the bf16 MFMA GEMMs: operand layouts, LDS images, the LDS-DMA
+// plan, the 128x128 DMA main loop and the 256x256 ping-pong tile with their fused epilogues, and
+// the GEMM kernels themselves.  Device code only: the host side shared with csrc/experiments
+// (the weak references to it, the gemm_host helpers, set_extents) is in gemm_host.h.  Shared by
+// the production launchers (gemm_bf16.hip) and the experiment kernels (csrc/experiments/, built
+// only with NNMPI_BUILD_EXPERIMENTS=1).  See gemm_bf16.hip for the design notes.
 #pragma once
 #include "common.h"
 #include "kernels.h"
@@ -661,6 +662,12 @@ struct DmaPlan {
     }
   }
 };
+
+// The grouped launches' tile (bwd_group_kernel and wgrad_multi_kernel run dma_gemm_tile with
+// these): 128x128, 8 waves as 2 x 4, a 2-stage ring -- 64 KiB, two blocks per CU
+constexpr int GRP_BM = 128, GRP_BN = 128, GRP_WGM = 2, GRP_WGN = 4, GRP_NS = 2;
+constexpr int GRP_THREADS = 64 * GRP_WGM * GRP_WGN;
+constexpr int GRP_SMEM = GRP_NS * (GRP_BM + GRP_BN) * GEMM_BK * 2;
 
 // One output tile (tx, ty) of K-split `split` — the body shared by the standalone GEMM launch
 // and the grouped backward launch (bwd_group_kernel).
@@ -1374,41 +1381,6 @@ __global__ void __launch_bounds__(PP_THREADS) gemm_bf16_pp256_kernel(GemmParams 
   const int gx = gridDim.x, gy = gridDim.y;
   pp256_tile<LA, LB, EPI, ACT, BIASGRAD, LATE_LGKM, GM, ISSUE, PF>(
       p, smem, xcd_remap(blockIdx.y * gx + blockIdx.x, gx * gy), gx, gy, blockIdx.z);
-}
-
-// ---- experiment kernels (csrc/experiments/gemm_experiments.hip) ------------------------------
-// Built into the library only with NNMPI_EXPERIMENTS=1 (_build.py); weak references here, so a
-// production build links without them and every entry point below is a null pointer.
-// variant 19..24: the deep-ring twin of the 256x256 kernel (docs/PERF.md §4)
-__attribute__((weak)) hipError_t exp_pp256_ring(int variant, int la, int lb, int epi, int act,
-                                                int bg, GemmParams p, dim3 grid, hipStream_t s);
-// gemm_bf16_pp256_pair_kernel (off by default even when built: NNMPI_PAIR=1)
-__attribute__((weak)) void exp_set_wide_pair(int on);
-__attribute__((weak)) bool exp_wide_pair_wgrad_ok(int rows, int out_f, int in_f);
-__attribute__((weak)) bool exp_wide_pair_dgrad_ok(int rows, int out_f, int in_f);
-__attribute__((weak)) hipError_t exp_wide_pair(const WgradArgs& w1, const DgradArgs* dg,
-                                               const WgradArgs* w2, hipStream_t s);
-__attribute__((weak)) hipError_t exp_fwd_stamped(const bf16* X, int ldx, const bf16* W, int ldw,
-                                                 const float* bias, bf16* Y, int ldy, int M, int N,
-                                                 int K, unsigned long long* stamps, hipStream_t s);
-
-// ---- host helpers shared with csrc/experiments (defined in gemm_bf16.hip) ----
-namespace gemm_host {
-// the weight-gradient GEMM of a WgradArgs and its pending split-K combine (returns the splits)
-int make_wgrad(const WgradArgs& a, GemmParams& p, SlabReduce& pending);
-int pick_tile(int M, int N);
-int wgrad_tile(int M, int N);
-// the production kernel selection is in effect (LDS-DMA path, no forced tile or variant)
-bool default_path();
-}  // namespace gemm_host
-
-template <int LA, int LB>
-static inline void set_extents(GemmParams& p) {
-  // storage extents (bytes) of the operands, for the buffer-resource range checks
-  const long long a = (LA == KMAJ) ? ((long long)(p.M - 1) * p.lda + p.K) : ((long long)(p.K - 1) * p.lda + p.M);
-  const long long b = (LB == KMAJ) ? ((long long)(p.N - 1) * p.ldb + p.K) : ((long long)(p.K - 1) * p.ldb + p.N);
-  p.a_bytes = (unsigned)std::min<long long>(a * 2, DMA_OOB - 16);
-  p.b_bytes = (unsigned)std::min<long long>(b * 2, DMA_OOB - 16);
 }
 
 }  // namespace nnmpi
