@@ -402,6 +402,24 @@ hipError_t adam_update_bf16grad(float* p, const bf16* g, float* m, float* v, bf1
                                 const SgdPack* pack = nullptr);
 // ++*t (an int32 in device memory), then hp[ADAM_BC1] = 1 - beta1^t, hp[ADAM_BC2] = 1 - beta2^t
 hipError_t adam_tick(float* hp, int* t, hipStream_t s);
+// ---- global-norm gradient clipping (optim.hip: the layout comment at its top) ----
+enum ClipSlot : int {
+  CLIP_MAX_NORM = 0, CLIP_BASE_GS = 1, CLIP_LAST_NORM = 2, CLIP_LAST_COEF = 3, CLIP_STATE_LEN = 4
+};
+constexpr int CLIP_MAX_PARTS = 1024;   // most partials grad_sumsq writes
+// blocks (= double partials written to part[0 ..)) of grad_sumsq over n elements: a function of
+// n alone, at most CLIP_MAX_PARTS
+int sumsq_parts(long long n);
+// part[b] = sum of g[i]^2 over block b's grid-stride elements, in double, fixed order, no
+// atomics; n % 4 == 0 (16-byte / 8-byte accesses), n == 0 writes one zero partial
+hipError_t grad_sumsq(const float* g, long long n, double* part, hipStream_t s);
+hipError_t grad_sumsq_bf16(const bf16* g, long long n, double* part, hipStream_t s);
+// *out = part[0] + ... + part[nparts - 1], one block, fixed order (ZeRO-1: a rank's own sum)
+hipError_t sumsq_reduce(const double* part, int nparts, double* out, hipStream_t s);
+// total = the same fixed-order sum; norm = base_gs * sqrt(total); coef = min(1, max_norm /
+// (norm + 1e-6)) keeping NaN; hp[4] = base_gs * coef; clip_state[2], [3] = norm, coef
+hipError_t clip_finalize(float* hp, float* clip_state, const double* part, int nparts,
+                         hipStream_t s);
 hipError_t cast_f32_bf16(const float* x, bf16* y, long long n, hipStream_t s);
 hipError_t scale_f32(float* x, long long n, float a, hipStream_t s);
 hipError_t cast_bf16_f32(const bf16* x, float* y, long long n, hipStream_t s);

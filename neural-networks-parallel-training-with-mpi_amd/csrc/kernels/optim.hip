@@ -21,6 +21,17 @@
 // The step number t is an int32 in device memory (a float stops counting at 2^24): adam_tick
 // advances it and refreshes bc1 / bc2 once per optimizer step, as a node of the step's graph, so
 // a replayed graph of N steps advances t N times; the update kernels read only the tensor.
+//
+// Global-norm gradient clipping (torch.nn.utils.clip_grad_norm_) changes no update kernel: they
+// all multiply the gradient by slot 4, so a clipped step runs grad_sumsq over the reduced
+// gradient and then clip_finalize, which writes slot 4 = base scale x clip coefficient ahead of
+// the update, on the device and inside the step's graph.  The clip-state tensor has
+// CLIP_STATE_LEN = 4 fp32 slots (ClipSlot, kernels.h):
+//
+//    0 max_norm      1 base gradient scale (what slot 4 holds without clipping; the host writes
+//                      it wherever it writes slot 4)
+//    2 last_norm     3 last_coef        -- written by clip_finalize: the pre-clip norm of the
+//                                          scaled gradient and min(1, max_norm / (norm + 1e-6))
 #include "common.h"
 #include "kernels.h"
 #include "knobs.h"
@@ -442,6 +453,102 @@ __global__ void checksum_final(double* part, int nb, double* out) {
     for (int i = 0; i < nb; ++i) s += part[i];
     *out = s;
   }
+}
+
+// ---- global-norm clipping ----
+// Sum of squares of n gradient elements, one double partial per block.  Each fp32 (or bf16)
+// square is exact in double, so the only rounding is in the additions -- all of fixed order: a
+// thread's grid-stride elements in index order, then the block's LDS tree.  The grid depends on
+// n alone (sumsq_parts), so the same n and bits give the same partials on every run and rank.
+template <typename TG>
+__global__ void __launch_bounds__(256) grad_sumsq_kernel(TG* __restrict__ g, long long n4,
+                                                         double* __restrict__ part) {
+  __shared__ double red[256];
+  double s = 0.0;
+  const long long stride = (long long)gridDim.x * blockDim.x;
+  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride) {
+    const f32x4 v = load_grad4(g, i);
+#pragma unroll
+    for (int r = 0; r < 4; ++r) s += (double)v[r] * (double)v[r];
+  }
+  red[threadIdx.x] = s;
+  __syncthreads();
+  for (int o = 128; o > 0; o >>= 1) {
+    if ((int)threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) part[blockIdx.x] = red[0];
+}
+
+// One block's fixed-order sum of n doubles (every thread returns it): thread t adds part[t],
+// part[t + 256], ... in that order, then the LDS tree.
+__device__ __forceinline__ double block_sum_ordered(const double* __restrict__ part, int n,
+                                                    double* red) {
+  double s = 0.0;
+  for (int i = threadIdx.x; i < n; i += 256) s += part[i];
+  red[threadIdx.x] = s;
+  __syncthreads();
+  for (int o = 128; o > 0; o >>= 1) {
+    if ((int)threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
+    __syncthreads();
+  }
+  return red[0];
+}
+
+__global__ void __launch_bounds__(256) sumsq_reduce_kernel(const double* __restrict__ part, int n,
+                                                           double* __restrict__ out) {
+  __shared__ double red[256];
+  const double total = block_sum_ordered(part, n, red);
+  if (threadIdx.x == 0) *out = total;
+}
+
+__global__ void __launch_bounds__(256) clip_finalize_kernel(float* __restrict__ hp,
+                                                            float* __restrict__ cs,
+                                                            const double* __restrict__ part,
+                                                            int n) {
+  __shared__ double red[256];
+  const double total = block_sum_ordered(part, n, red);
+  if (threadIdx.x != 0) return;
+  const double max_norm = (double)cs[CLIP_MAX_NORM], base = (double)cs[CLIP_BASE_GS];
+  const double norm = base * sqrt(total);
+  double coef = max_norm / (norm + 1e-6);
+  // torch.clamp(max=1): a NaN stays a NaN (fmin would return 1)
+  coef = coef < 1.0 ? coef : (coef >= 1.0 ? 1.0 : coef);
+  hp[4] = (float)(base * coef);   // coef == 1: the base scale, bit for bit
+  cs[CLIP_LAST_NORM] = (float)norm;
+  cs[CLIP_LAST_COEF] = (float)coef;
+}
+
+int sumsq_parts(long long n) {
+  const long long b = (n / 4 + 255) / 256;
+  return (int)std::max<long long>(1, std::min<long long>(b, CLIP_MAX_PARTS));
+}
+
+hipError_t grad_sumsq(const float* g, long long n, double* part, hipStream_t s) {
+  if (!g || !part || n < 0 || n % 4 != 0) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(grad_sumsq_kernel<const float>, dim3(sumsq_parts(n)), dim3(256), 0, s, g,
+                     n / 4, part);
+  return hipGetLastError();
+}
+
+hipError_t grad_sumsq_bf16(const bf16* g, long long n, double* part, hipStream_t s) {
+  if (!g || !part || n < 0 || n % 4 != 0) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(grad_sumsq_kernel<const bf16>, dim3(sumsq_parts(n)), dim3(256), 0, s, g,
+                     n / 4, part);
+  return hipGetLastError();
+}
+
+hipError_t sumsq_reduce(const double* part, int nparts, double* out, hipStream_t s) {
+  if (!part || !out || nparts < 0) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(sumsq_reduce_kernel, dim3(1), dim3(256), 0, s, part, nparts, out);
+  return hipGetLastError();
+}
+
+hipError_t clip_finalize(float* hp, float* clip_state, const double* part, int nparts,
+                         hipStream_t s) {
+  if (!hp || !clip_state || !part || nparts < 0) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(clip_finalize_kernel, dim3(1), dim3(256), 0, s, hp, clip_state, part, nparts);
+  return hipGetLastError();
 }
 
 hipError_t cast_f32_bf16(const float* x, bf16* y, long long n, hipStream_t s) {

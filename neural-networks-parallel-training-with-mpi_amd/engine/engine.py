@@ -13,7 +13,9 @@ One step (per rank), replacing the reference's hot loop ``ref.py:155-211`` (Data
     join      compute stream waits for the comm stream
     update    fused SGD-momentum over the whole arena (1/P folded in, bf16 shadow refreshed,
               gradients zeroed for the next step); or Adam / AdamW, one pass of the same shape
-              behind a one-thread launch that advances the device step number (optimizer.py)
+              behind a one-thread launch that advances the device step number (optimizer.py);
+              with clip_grad_norm, the gradient's norm and a one-block launch that rewrites
+              the gradient-scale slot run right before it
 
 All buffers are allocated once (rows capacity), so on the GPU the steady-state step is
 allocation-free and is captured into ONE hipGraph (kernels + RCCL + cross-stream events) that
@@ -86,9 +88,13 @@ class MLPEngine:
                  use_tiny: Optional[bool] = None, overlap: bool = True, fuse_sgd: bool = True,
                  grouped: bool = True, rowband_overlap: bool = False,
                  rowband_plan: Optional[int] = None, optimizer: str = "sgd", beta1: float = 0.9,
-                 beta2: float = 0.999, eps: float = 1e-8):
+                 beta2: float = 0.999, eps: float = 1e-8,
+                 clip_grad_norm: Optional[float] = None):
         """``optimizer``: ``sgd`` (momentum / dampening / nesterov apply), ``adam`` or ``adamw``
-        (beta1 / beta2 / eps apply; ``momentum`` is ignored).  ``weight_decay`` is shared."""
+        (beta1 / beta2 / eps apply; ``momentum`` is ignored).  ``weight_decay`` is shared.
+        ``clip_grad_norm``: clip the (reduced, averaged) gradient to this global L2 norm before
+        every update, as ``torch.nn.utils.clip_grad_norm_`` does -- norm and coefficient are
+        computed on the device inside the step (engine/optimizer.py); None: off."""
         self.spec, self.arena, self.ops, self.sync = spec, arena, ops, sync
         self.device = torch.device(device)
         self.dtype = dtype
@@ -126,9 +132,13 @@ class MLPEngine:
         self.hp = (adam_hparams(lr, beta1, beta2, eps, weight_decay, dev) if adam else
                    sgd_hparams(lr, momentum, dampening, weight_decay, dev))
         # every update site goes through this object (engine/optimizer.py)
-        self.opt = make_optimizer(optimizer, ops, arena, self.hp, self.nesterov)
+        if clip_grad_norm is not None and not float(clip_grad_norm) > 0:    # (also NaN)
+            raise ValueError(f"clip_grad_norm must be > 0, got {clip_grad_norm}")
+        self.opt = make_optimizer(optimizer, ops, arena, self.hp, self.nesterov,
+                                  clip_grad_norm=clip_grad_norm)
         # Adam cannot ride in the kernels' fused epilogues (SgdFuse: one state buffer, the SGD
-        # formula): every schedule runs in its unfused form, the update a separate pass
+        # formula): every schedule runs in its unfused form, the update a separate pass.  So
+        # does a clipped step: its coefficient needs the whole reduced gradient
         fuse_sgd = bool(fuse_sgd) and self.opt.fusable
         # ---- what the configuration allows; _schedule() picks per batch from these ----------
         self.overlap = bool(overlap) and self.is_cuda and not self.use_tiny
@@ -202,7 +212,7 @@ class MLPEngine:
         self.inv_count = 1.0
         self.loss_scale = 1.0
         self.timer = None   # utils.metrics.EventTimer: per-phase breakdown (steps run eagerly)
-        self._acc = self._eval_gw = self._loss_hist = None   # allocated on first use
+        self._acc = self._eval_gw = self._loss_hist = self._clip_hist = None   # allocated on first use
         self._n_acc = 0
 
     @property
@@ -272,6 +282,9 @@ class MLPEngine:
             for k, v in ((0, lr), (1, momentum), (4, grad_scale)):
                 if v is not None:
                     self.hp[k:k + 1].fill_(float(v))
+            if grad_scale is not None and self.opt.clipping:
+                # clip_finalize rewrites slot 4 every step as this base scale x the coefficient
+                self.opt.clip_state[1:2].fill_(float(grad_scale))
 
     def set_scales(self, inv_count: float, loss_scale: float, grad_scale: float):
         """Loss-gradient scale (1/count), reported-loss scale, optimizer gradient scale (1/P)."""
@@ -476,6 +489,7 @@ class MLPEngine:
             self.sync.launch_bucket(b, self.stream)
         self.sync.finish()
         self._mark("comm")
+        self.opt.clip()            # (clipping off: launches nothing)
         self.opt.apply(first, zero_grad=zero_grad, images=images)
         if images is not None:
             self.images.mark(True)
@@ -766,6 +780,10 @@ class MLPEngine:
     def _chunks(self, n: int, chunk: int):
         return [min(chunk, n - k) for k in range(0, n, chunk)]
 
+    def _keep_clip(self, dst: torch.Tensor):
+        """dst[0, :] = (norm, coefficient) of the step just issued (a copy on the stream)."""
+        dst.view(-1)[:2].copy_(self.opt.clip_state[2:4])
+
     def prepare_steps(self, n: int, chunk: int = 16, losses: bool = False):
         """Capture (without running) every graph that run_steps(n, chunk) will replay
         (``losses``: the form that records every step's loss, see run_steps)."""
@@ -777,20 +795,27 @@ class MLPEngine:
                 if key not in self._graphs:
                     self._graphs[key] = self._capture(c, hist=losses)
 
-    def run_steps(self, n: int, chunk: int = 16, losses: Optional[torch.Tensor] = None):
+    def run_steps(self, n: int, chunk: int = 16, losses: Optional[torch.Tensor] = None,
+                  clips: Optional[torch.Tensor] = None):
         """n optimizer steps (asynchronous on the GPU).  In graph mode the steps are replayed as
         graphs of up to `chunk` consecutive steps; results are identical to n step() calls.
 
         ``losses``: a device fp32 tensor of >= n entries; step k's loss (what loss() would
         return right after it) lands in losses[k] -- per-step losses without a host sync per
         step (the compat trainer's full-batch epochs).  Written on the engine's stream:
-        synchronize() before reading them on the host."""
+        synchronize() before reading them on the host.  ``clips`` (with ``losses``, under
+        clip_grad_norm): a device fp32 tensor [>= n, 2]; step k's pre-clip gradient norm and
+        clip coefficient land in clips[k] the same way."""
         k0 = 0
+        if clips is not None and (losses is None or not self.opt.clipping):
+            raise ValueError("run_steps(clips=) needs losses= and an engine with clip_grad_norm")
 
         def keep(k):
             if losses is not None:
                 with self._on_stream():
                     losses[k:k + 1].copy_(self.loss_out[:1])
+                    if clips is not None:
+                        self._keep_clip(clips[k])
         if not (self.is_cuda and self.use_graph and self.timer is None):
             for k in range(n):
                 self.step()
@@ -815,6 +840,8 @@ class MLPEngine:
                     int(self.stream.cuda_stream))
                 if hist:
                     losses[k0:k0 + c].copy_(self._loss_hist[:c])
+                    if clips is not None:
+                        clips[k0:k0 + c, :2].copy_(self._clip_hist[:c])
                 self._steps += c
                 k0 += c
 
@@ -860,12 +887,18 @@ class MLPEngine:
                 self._loss_hist = torch.zeros(LOSS_HIST_MAX, dtype=torch.float32, device=self.device)
             if nsteps > LOSS_HIST_MAX:
                 raise ValueError(f"loss-recording graphs hold at most {LOSS_HIST_MAX} steps")
+            # under clipping each step's (norm, coefficient) is recorded the same way
+            if self.opt.clipping and self._clip_hist is None:
+                self._clip_hist = torch.zeros(LOSS_HIST_MAX, 2, dtype=torch.float32,
+                                              device=self.device)
 
         def body():
             for k in range(nsteps):
                 self._step_body(False)
                 if hist:
                     self._loss_hist[k:k + 1].copy_(self.loss_out[:1])
+                    if self.opt.clipping:
+                        self._keep_clip(self._clip_hist[k])
         return self._capture_fn(body)
 
     def _capture_fn(self, body):
@@ -947,7 +980,7 @@ class MLPEngine:
             for i in reversed(range(self.L)):
                 self.sync.ready(i)
             self.sync.finish()
-            self.pipe.update_all(first)
+            self.pipe.update_all(first)      # (clips once, on the accumulated sum)
         self.images.mark(False)
         self._n_acc = 0
         self._steps += 1
@@ -999,6 +1032,22 @@ class MLPEngine:
             self.stream.synchronize()
         self.check_device_errors()
         return float(self.loss_out[0].item())
+
+    def _clip_slot(self, k: int) -> float:
+        if not self.opt.clipping:
+            raise RuntimeError("gradient clipping is off (MLPEngine(clip_grad_norm=...))")
+        if self.is_cuda:
+            self.stream.synchronize()
+        return float(self.opt.clip_state[k].item())
+
+    def grad_norm(self) -> float:
+        """Global L2 norm of the last step's reduced, averaged gradient, before clipping (host
+        sync).  Raises when clipping is off: nothing computes a norm then."""
+        return self._clip_slot(2)
+
+    def clip_coef(self) -> float:
+        """The last step's clip coefficient min(1, max_norm / (norm + 1e-6)) (host sync)."""
+        return self._clip_slot(3)
 
     def synchronize(self, check: bool = True):
         """Wait for the engine's stream.  ``check``: then raise if a column-split row-band step

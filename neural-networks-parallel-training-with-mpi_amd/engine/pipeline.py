@@ -3,6 +3,9 @@ collectives, overlapped row-band): as soon as a bucket's last gradient is writte
 all-reduce starts on the comm stream, followed there by that bucket's SGD update (gated on the
 last reader of its weights, ``ev_wfree``), so only the final bucket's all-reduce + update remain
 on the critical path.  With one rank the update of the whole arena runs once at the end.
+Under gradient clipping (engine/optimizer.py) the collectives overlap the backward all the same,
+but no update is issued before the join: the clip coefficient needs the whole reduced gradient,
+so one norm, one finalize and one update of the whole arena follow the join.
 
 Invariants (docs/ARCHITECTURE.md §1 records the hang at P = 2 and the capture crash at P = 3
 that breaking them caused):
@@ -71,6 +74,7 @@ class BucketPipeline:
         self.sgd_done = set()                 # buckets whose update is queued or issued
         self.reduced = {}                     # bucket index -> stream its collective completes on
         self.pending: List[Tuple[object, object]] = []   # (bucket, stream) updates not issued yet
+        self.held: List[object] = []          # clipping: reduced buckets, updated behind the join
         self.written16: List[Tuple[int, int]] = []       # arena ranges stored as bf16 payload
         self.waited = set()                   # partner layers the compute stream has waited for
         # keywords of every bucket update: the bf16 payload, the row-band images to refresh
@@ -90,8 +94,10 @@ class BucketPipeline:
     def update_all(self, first: bool):
         """Optimizer update of the whole arena (or, sharded, of this rank's slice + gathers)."""
         if self.sharded:
+            # (its clip follows the reduce-scatter, inside update())
             self.sync.update(self.ops, self.hp, self.nesterov, first, opt=self.opt)
         else:
+            self.opt.clip()        # (clipping off: launches nothing)
             self.opt.apply(first)
 
     def bucket_reduce(self, b, stream):
@@ -120,6 +126,11 @@ class BucketPipeline:
             rs = self.bucket_reduce(b, stream)
             if rs is None or rs is stream:
                 continue   # reduced on this stream already (single rank): update once at the end
+            if self.opt.clipping:
+                # the clip coefficient needs the whole reduced gradient: the collectives still
+                # overlap the backward, every update waits for join()
+                self.held.append(b)
+                continue
             self.pending.append((b, rs))
             self.sgd_done.add(b.index)
 
@@ -183,6 +194,15 @@ class BucketPipeline:
         buckets the comm stream did not update -- all of them on one rank: one pass."""
         tail, self.pending = self.pending, []
         self.sync.finish()   # joins the comm stream into the compute stream
+        if self.held:
+            # clipping, per-bucket collectives: one norm of the whole reduced gradient (of the
+            # bf16 payload when that is what the update reads), one finalize, one update
+            self.held = []
+            if joined is not None:
+                joined()
+            self.opt.clip(grad_bf16=self.upd_grad)
+            self.sgd(0, self.arena.numel)
+            return
         runs: List[List[int]] = []           # [start, end) of each contiguous range
         for b in sorted((b for b, _ in tail), key=lambda b: b.offset):
             if runs and runs[-1][1] == b.offset:

@@ -65,6 +65,10 @@ class TrainResult:
     steps: int = 0
     phase_ms: Optional[dict] = None   # --profile_steps: mean ms per step per phase
     schedule: Optional[dict] = None   # what the engine chose: payload, sync, grouped/deferred
+    # --clip_grad_norm: per epoch, the last step's pre-clip gradient norm and clip coefficient
+    # (also under schedule["grad_norms"] / ["clip_coefs"], which travels with the rank results)
+    grad_norms: List[float] = field(default_factory=list)
+    clip_coefs: List[float] = field(default_factory=list)
 
 
 def dist_train(args) -> Optional[TrainResult]:
@@ -412,7 +416,21 @@ def _run(j: Job) -> TrainResult:
                     rows_capacity=max(cap, 1), lr=cfg.lr, momentum=cfg.momentum,
                     dampening=cfg.dampening, weight_decay=cfg.weight_decay,
                     nesterov=cfg.nesterov, use_graph=cfg.graph, overlap=cfg.overlap,
-                    optimizer=cfg.optimizer, beta1=cfg.beta1, beta2=cfg.beta2, eps=cfg.eps)
+                    optimizer=cfg.optimizer, beta1=cfg.beta1, beta2=cfg.beta2, eps=cfg.eps,
+                    clip_grad_norm=cfg.clip_grad_norm)
+    clipping = cfg.clip_grad_norm is not None
+
+    def clip_metrics(norm=None, coef=None) -> dict:
+        """--clip_grad_norm: the pre-clip norm of the averaged gradient and the coefficient of
+        the epoch's last step (read from the device when not given), also kept in the result;
+        nothing without the flag."""
+        if not clipping:
+            return {}
+        m = {"grad_norm": eng.grad_norm() if norm is None else norm,
+             "clip_coef": eng.clip_coef() if coef is None else coef}
+        res.grad_norms.append(m["grad_norm"])
+        res.clip_coefs.append(m["clip_coef"])
+        return m
     eng.steps_done = steps_done      # (also the optimizer's device-side step number)
     if cfg.profile_steps:
         from ..utils.metrics import EventTimer
@@ -457,6 +475,9 @@ def _run(j: Job) -> TrainResult:
             eng.load_batch(Xc, Y, labels)
             eng.set_scales(*loss_scales(cfg, eng.rows, list(train_counts), cfg.widths[-1]))
             hist = torch.zeros(FAST_EPOCHS, dtype=torch.float32, device=j.device)
+            # (each step's norm and coefficient recorded on the device, as its loss is)
+            chist = (torch.zeros(FAST_EPOCHS, 2, dtype=torch.float32, device=j.device)
+                     if clipping else None)
             epoch = start_epoch
             # epochs per replay: the watchdog is kicked once per replay, so with several ranks a
             # replay must stay well inside timeout_s -- start small, then size it (a power of two,
@@ -465,9 +486,10 @@ def _run(j: Job) -> TrainResult:
             while epoch < cfg.nepochs:
                 c = min(per_replay, cfg.nepochs - epoch)
                 t0 = time.perf_counter()
-                eng.run_steps(c, c, losses=hist)
+                eng.run_steps(c, c, losses=hist, clips=chist)
                 eng.synchronize()            # the losses are written on the engine's stream
                 vals = hist[:c].tolist()
+                cvals = chist[:c].tolist() if clipping else None
                 dt = (time.perf_counter() - t0) / c
                 if wd:
                     wd.kick()
@@ -483,7 +505,8 @@ def _run(j: Job) -> TrainResult:
                                   samples_per_s=sps, world=world,
                                   parallel_efficiency=parallel_efficiency(sps, world,
                                                                           cfg.ref_samples_per_s),
-                                  **cvol, val_loss=None)
+                                  **cvol, val_loss=None,
+                                  **(clip_metrics(*cvals[k]) if clipping else {}))
                 epoch += c
         for epoch in range(start_epoch, cfg.nepochs if not fast else start_epoch):
             if fault is not None and epoch == fault:
@@ -575,7 +598,8 @@ def _run(j: Job) -> TrainResult:
                           samples_per_s=sps, world=world,
                           parallel_efficiency=parallel_efficiency(sps, world,
                                                                   cfg.ref_samples_per_s),
-                          **cvol, val_loss=res.val_losses[-1] if res.val_losses else None)
+                          **cvol, val_loss=res.val_losses[-1] if res.val_losses else None,
+                          **clip_metrics())
             if cfg.checkpoint and cfg.checkpoint_every and (epoch + 1) % cfg.checkpoint_every == 0:
                 _gather_state(eng, sync)
                 if rank == 0:
@@ -583,6 +607,9 @@ def _run(j: Job) -> TrainResult:
                 j.pg.barrier()
         eng.synchronize()
         res.steps = eng.steps_done
+        if clipping:
+            res.schedule.update(clip_grad_norm=float(cfg.clip_grad_norm),
+                                grad_norms=list(res.grad_norms), clip_coefs=list(res.clip_coefs))
         if eng.timer is not None:
             res.phase_ms = eng.timer.summary_ms()
             _print(cfg, rank, "[profile] mean ms per step: " +

@@ -25,6 +25,22 @@ class OpSet:
     # workspace sizes in bytes; the row-band kernel version that runs a model (0: none)
     tiny_workspace_bytes = wgrad_workspace_bytes = head_workspace_bytes = rowband_version = _zero
 
+    # ---- global-norm gradient clipping (csrc/kernels/optim.hip; TorchOps is the oracle) ----
+    def grad_sumsq(self, arena, part, offset: int = 0, numel=None, grad_bf16=None) -> int:
+        """Sum of squares of ``[offset, offset + numel)`` of the gradient (``grad_bf16``: of that
+        bf16 buffer instead of ``arena.grad``) as float64 partials in ``part``; returns how many
+        partials were written."""
+        raise NotImplementedError(f"{type(self).__name__}: grad_sumsq is not supported")
+
+    def sumsq_reduce(self, part, nparts: int, out):
+        """``out[0]`` = the fixed-order sum of ``part[:nparts]`` (float64)."""
+        raise NotImplementedError(f"{type(self).__name__}: sumsq_reduce is not supported")
+
+    def clip_finalize(self, hp, clip_state, part, nparts: int):
+        """From the summed partials: ``hp[4]`` = base scale x clip coefficient, and the norm and
+        the coefficient into ``clip_state`` ([max_norm, base_gs, last_norm, last_coef])."""
+        raise NotImplementedError(f"{type(self).__name__}: clip_finalize is not supported")
+
     def rowband_ok(self, rows, widths, act, loss) -> bool:
         """The whole forward + head + activation-gradient chain runs as one launch per step
         (see rowband.hip)."""

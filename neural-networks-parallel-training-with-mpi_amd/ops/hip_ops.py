@@ -464,6 +464,38 @@ class HipOps(OpSet):
                 pack.append((slot.offset - offset, M, N, _p(pf), _p(pd) if pd is not None else 0))
         return pack
 
+    # ---- global-norm clipping ----
+    def grad_sumsq(self, arena, part, offset: int = 0, numel: int = None, grad_bf16=None) -> int:
+        """One double partial per block into ``part`` (float64, >= CLIP_MAX_PARTS entries); the
+        block count depends on the length alone.  Returns the number of partials."""
+        n = arena.numel - offset if numel is None else numel
+        _check(n % 4 == 0 and offset % 4 == 0, f"grad_sumsq: offset and numel % 4 == 0 ({offset}, {n})")
+        _check(0 <= offset and 0 <= n and offset + n <= arena.numel,
+               "grad_sumsq: range outside the arena")
+        _check(part.dtype == torch.float64 and part.numel() >= int(self.lib.CLIP_MAX_PARTS),
+               "grad_sumsq: a float64 partial buffer of CLIP_MAX_PARTS entries")
+        if grad_bf16 is not None:
+            _check(grad_bf16.dtype == torch.bfloat16 and grad_bf16.numel() >= offset + n,
+                   "grad_sumsq: bf16 gradient buffer too small")
+            self.lib.grad_sumsq_bf16(_p(grad_bf16) + 2 * offset, n, _p(part), self.stream)
+        else:
+            self.lib.grad_sumsq(_p(arena.grad) + 4 * offset, n, _p(part), self.stream)
+        return int(self.lib.sumsq_parts(n))
+
+    def sumsq_reduce(self, part, nparts: int, out):
+        _check(part.dtype == torch.float64 and out.dtype == torch.float64 and out.numel() >= 1 and
+               0 <= nparts <= part.numel(), "sumsq_reduce: float64 partials and output")
+        self.lib.sumsq_reduce(_p(part), int(nparts), _p(out), self.stream)
+
+    def clip_finalize(self, hp, clip_state, part, nparts: int):
+        _check(hp.dtype == torch.float32 and hp.numel() >= 5 and
+               clip_state.dtype == torch.float32 and
+               clip_state.numel() >= int(self.lib.CLIP_STATE_LEN),
+               "clip_finalize: fp32 hyper-parameters and the 4-slot clip state")
+        _check(part.dtype == torch.float64 and 0 <= nparts <= part.numel(),
+               "clip_finalize: float64 partials")
+        self.lib.clip_finalize(_p(hp), _p(clip_state), _p(part), int(nparts), self.stream)
+
     def adam_tick(self, hp, t):
         """Advance the device step counter ``t`` (int32) and refresh the bias corrections in
         ``hp`` (one single-thread launch: capturable, so a replayed graph counts its steps)."""

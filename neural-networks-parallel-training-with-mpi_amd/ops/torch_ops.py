@@ -110,6 +110,36 @@ class TorchOps(OpSet):
             if zero_grad:
                 g.zero_()
 
+    # ---- global-norm clipping: the float64 oracle of grad_sumsq / clip_finalize (optim.hip) -----
+    def grad_sumsq(self, arena, part, offset: int = 0, numel: int = None, grad_bf16=None) -> int:
+        n = arena.numel - offset if numel is None else numel
+        g = (arena.grad if grad_bf16 is None else grad_bf16)[offset:offset + n]
+        with torch.no_grad():
+            g = g.double()
+            part[:1].copy_((g * g).sum().reshape(1))
+        return 1
+
+    def sumsq_reduce(self, part, nparts: int, out):
+        with torch.no_grad():
+            out[:1].copy_(part[:nparts].sum().reshape(1))
+
+    def clip_finalize(self, hp, clip_state, part, nparts: int):
+        """The kernel's formula in Python doubles: the partials summed in index order (ZeRO-1:
+        rank order), min(1, .) that keeps a NaN as torch.clamp(max=1) does, and ``hp[4]`` = the
+        base scale bit for bit when the coefficient is 1."""
+        total = 0.0
+        for v in part[:nparts].tolist():
+            total += v
+        max_norm, base = [float(v) for v in clip_state[:2].tolist()]
+        norm = base * (total ** 0.5 if total == total and total >= 0 else float("nan"))
+        coef = max_norm / (norm + 1e-6)
+        coef = coef if coef < 1.0 else (1.0 if coef >= 1.0 else coef)
+        # (rounded as the kernel's (float) casts round: a double beyond fp32 becomes inf)
+        out = torch.tensor([base * coef, norm, coef], dtype=torch.float64).to(torch.float32)
+        with torch.no_grad():
+            hp[4:5].copy_(out[0:1])
+            clip_state[2:4].copy_(out[1:3])
+
     # ---- Adam / AdamW: hp in the Adam layout (engine/optimizer.py ADAM_*, optim.hip) ----------
     def adam_tick(self, hp, t):
         """t += 1 (int32 tensor of one element); hp[6], hp[7] = 1 - beta1^t, 1 - beta2^t, computed

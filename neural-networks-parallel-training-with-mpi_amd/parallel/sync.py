@@ -448,8 +448,17 @@ class ShardedSync(GradSync):
         if self.comm is not None:
             h = self.native.stream_handle()
             self._reduce_scatter(h)
+            # clipping: the sum of squares of this rank's reduced slice, then the P sums
+            # all-gathered bitwise (a double travels as two fp32 words) on the same stream and
+            # added in rank order -- every rank holds the same coefficient bit for bit
+            opt.clip(offset=self.off, numel=self.shard, gather=(
+                self.world, self.rank,
+                lambda buf: self.comm.allgather(buf.data_ptr() + 8 * self.rank, buf.data_ptr(),
+                                                2, 0, h)))
         else:
             dist.all_reduce(ar.grad, group=self.group)
+            # the full gradient is here: the norm the all-reduce path takes, no extra collective
+            opt.clip()
         opt.apply(first, offset=self.off, numel=self.shard)
         if self.comm is not None:
             if ar.shadow is not None:

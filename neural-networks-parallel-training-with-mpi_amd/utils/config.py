@@ -57,6 +57,8 @@ class TrainConfig:
     beta1: float = 0.9
     beta2: float = 0.999
     eps: float = 1e-8
+    # clip the averaged gradient to this global L2 norm before every update (None: off)
+    clip_grad_norm: Optional[float] = None
     # --- data ---
     n_samples: int = 16
     n_features: Optional[int] = None  # defaults to widths[0]
@@ -144,6 +146,10 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--beta1", type=float, default=0.9, help="Adam beta1 [0.9]")
     p.add_argument("--beta2", type=float, default=0.999, help="Adam beta2 [0.999]")
     p.add_argument("--eps", type=float, default=1e-8, help="Adam eps [1e-8]")
+    p.add_argument("--clip_grad_norm", type=float, default=None, metavar="G",
+                   help="clip the gradient to global L2 norm G before every update "
+                        "(torch.nn.utils.clip_grad_norm_ semantics, any optimizer, computed on "
+                        "the device inside the step) [off]")
     p.add_argument("--n_samples", type=int, default=None)
     p.add_argument("--n_features", type=int, default=None)
     p.add_argument("--noise", type=float, default=1.0)
@@ -277,6 +283,8 @@ def validate(cfg: TrainConfig) -> None:
         raise ValueError(f"beta1 and beta2 must be in [0, 1), got {cfg.beta1}, {cfg.beta2}")
     if not cfg.eps > 0:
         raise ValueError(f"eps must be > 0, got {cfg.eps}")
+    if cfg.clip_grad_norm is not None and not float(cfg.clip_grad_norm) > 0:    # (also NaN)
+        raise ValueError(f"clip_grad_norm must be > 0, got {cfg.clip_grad_norm}")
     if cfg.optimizer != "sgd" and (cfg.nesterov or cfg.dampening != 0):
         raise ValueError(f"--nesterov / --dampening are SGD options, not for {cfg.optimizer}")
     if cfg.lr < 0 or cfg.momentum < 0 or cfg.weight_decay < 0:
