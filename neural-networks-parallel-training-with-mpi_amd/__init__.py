@@ -13,12 +13,15 @@ Public surface (compatible with the reference):
 * :class:`MLP` — ``MLP()`` with attribute ``layers`` (``nn.Sequential``) and reference
   state_dict keys ``layers.{i}.weight/bias``.
 * :class:`RegressionDataset` — ``RegressionDataset(X, y, scale_data=True)``.
+* :class:`Predictor` — outputs, loss and accuracy / MAE of a saved ``state_dict`` (not in the
+  reference, which never uses a trained model).
 """
 __version__ = "0.1.0"
 
 from .models.mlp import MLP, MLPSpec  # noqa: E402,F401
 from .data.dataset import RegressionDataset  # noqa: E402,F401
 from .utils.config import TrainConfig, build_parser, config_from_args  # noqa: E402,F401
+from .predictor import Predictor  # noqa: E402,F401
 
 
 def dist_train(args):

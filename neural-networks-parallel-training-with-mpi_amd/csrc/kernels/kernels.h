@@ -333,6 +333,27 @@ hipError_t head_general(const void* a, int a_bf16, int rows, int in, const float
                         int act_prev, void* dz_out, float* gW, float* gb, float* dlogits_out,
                         float* ws, float loss_scale, float* loss_out, hipStream_t s);
 
+// ---- forward-only output layer for evaluation / prediction (head_eval.hip), any head shape ----
+// a: [rows][in] (bf16 if a_bf16 else fp32, leading dimension lda); W [out][in] fp32, b [out].
+// loss: LOSS_MSE (y [rows][out]), LOSS_XENT (labels [rows], only ever compared with an output
+// index) or -1 (no targets read).  Optional outputs: logits_out [rows][ldl] (ldl >= out), pred_out
+// [rows] int32 (torch.argmax's rule), metrics = 4 doubles [loss_sum, correct, abs_err_sum, rows]
+// (accumulate != 0: added to, else overwritten; the slot a loss does not define is 0), summed in
+// double in a fixed order.  ws: head_eval_workspace_bytes (needed with metrics only).
+// hipErrorInvalidValue before any launch for: a null W / b / workspace, a null a / needed target
+// with rows > 0,
+// lda < in, ldl < out, in > 8192, rows < 0, and bf16 rows that are not in % 8 == 0 and 16-byte
+// aligned (fp32 rows of any width and alignment run, on a scalar-load form where needed).
+// rows == 0 reads nothing and still zeroes metrics unless accumulate.
+size_t head_eval_workspace_bytes(int rows, int in, int out);
+// the kernel form a call with these operands runs: 0 scalar-load VALU, 1 16-byte-load VALU,
+// 2 matrix cores (bf16, in 512 / 1024, 2 <= out <= 16, 16-byte aligned a and W)
+int head_eval_form(const void* a, int a_bf16, int lda, int in, int out, const float* W);
+hipError_t head_eval(const void* a, int a_bf16, int lda, int rows, int in, const float* W,
+                     const float* b, int out, const float* y, const int64_t* labels, int loss,
+                     float* logits_out, int ldl, int* pred_out, double* metrics, int accumulate,
+                     float* ws, hipStream_t s);
+
 // ---- whole tiny MLP in one launch (tiny_mlp.hip), fp32, widths <= 16, layers <= 4 ----
 struct TinyMLPDesc {
   int n_layers;

@@ -212,7 +212,7 @@ class MLPEngine:
         self.inv_count = 1.0
         self.loss_scale = 1.0
         self.timer = None   # utils.metrics.EventTimer: per-phase breakdown (steps run eagerly)
-        self._acc = self._eval_gw = self._loss_hist = self._clip_hist = None   # allocated on first use
+        self._acc = self._eval_gw = self._loss_hist = self._clip_hist = self._ev = None   # allocated on first use
         self._n_acc = 0
 
     @property
@@ -1025,6 +1025,80 @@ class MLPEngine:
                     scale = 1.0
             total += self.loss() * scale
         return total, n
+
+    # ---------------- prediction / metrics (forward only, head_eval.hip) -----------------------
+    # Both run the hidden layers with the sequential GEMMs (_forward: the compute weights a
+    # training step would use; a tiny-path engine takes them too, in fp32) and then the
+    # forward-only head on the fp32 master of the last layer -- what evaluate() passes.  Neither
+    # is captured into a graph.  They leave parameters, optimizer state, gradients, dlogits,
+    # loss_out, the clip state and the step counters alone; like evaluate() they OVERWRITE the
+    # input and activation buffers: reload the training batch before the next step.
+    def _eval_buffers(self):
+        if self._ev is None:
+            w, dev = self.spec.widths, self.device
+            nws = max(1, self.ops.head_eval_workspace_bytes(self.R, w[-2], w[-1]) // 4 + 16)
+            with self._on_stream():     # filled on the stream that uses them
+                self._ev = {
+                    "metrics": torch.zeros(4, dtype=torch.float64, device=dev),
+                    "logits": torch.zeros(self.R, w[-1], dtype=torch.float32, device=dev),
+                    "pred": torch.zeros(self.R, dtype=torch.int32, device=dev),
+                    "ws": torch.zeros(nws, dtype=torch.float32, device=dev)}
+        return self._ev
+
+    def _eval_chunk(self, X, Y, labels, lo: int, hi: int, loss=None, **outputs):
+        """Rows lo..hi through the hidden layers and the forward-only head (on the stream);
+        ``loss``: the loss whose targets (loaded with the rows) the head reads, None: neither."""
+        self.load_batch(X[lo:hi], Y[lo:hi] if Y is not None else None,
+                        labels[lo:hi] if labels is not None else None)
+        rows, last = self.rows, self.L - 1
+        y, lab = self._targets(rows) if loss is not None else (None, None)
+        with self._on_stream(), torch.no_grad():
+            h = self._forward(self.X[:rows])
+            self.ops.head_eval(h, self.arena.weight(last), self.arena.bias(last), y, lab, loss,
+                               **outputs)
+
+    def predict(self, X: torch.Tensor, classes: bool = False) -> torch.Tensor:
+        """The model's outputs for the rows of ``X`` with the current parameters: fp32
+        ``[n, out]`` (logits under cross-entropy, the regression output under MSE), or with
+        ``classes=True`` the int64 argmax ``[n]`` (``torch.argmax``'s rule).  Chunked by the
+        row capacity; ``n == 0`` returns an empty tensor without a launch.  Overwrites the input
+        and activation buffers (see above); synchronises the engine's stream before returning."""
+        n, out_f = X.shape[0], self.spec.widths[-1]
+        res = (torch.empty(n, dtype=torch.int64, device=self.device) if classes else
+               torch.empty(n, out_f, dtype=torch.float32, device=self.device))
+        if n == 0:
+            return res
+        ev = self._eval_buffers()
+        for lo in range(0, n, self.R):
+            hi = min(n, lo + self.R)
+            rows = hi - lo
+            if classes:
+                self._eval_chunk(X, None, None, lo, hi, pred_out=ev["pred"][:rows])
+            else:
+                self._eval_chunk(X, None, None, lo, hi, logits_out=ev["logits"][:rows])
+            with self._on_stream(), torch.no_grad():
+                res[lo:hi].copy_(ev["pred"][:rows] if classes else ev["logits"][:rows])
+        self.synchronize()
+        return res
+
+    def evaluate_metrics(self, X: torch.Tensor, Y: Optional[torch.Tensor] = None,
+                         labels: Optional[torch.Tensor] = None) -> dict:
+        """Forward-only metrics over held-out rows, chunked by the row capacity: ``loss_sum``
+        (the per-row sums evaluate() returns), ``rows``, ``correct`` (cross-entropy: rows whose
+        argmax is the label, else 0) and ``abs_err_sum`` (MSE: sum of |output - target|, else 0)
+        as Python numbers.  Every chunk accumulates on the device (float64, fixed order): ONE host
+        synchronisation at the end.  Overwrites the input and activation buffers (see above)."""
+        n = X.shape[0]
+        if n == 0:
+            return {"loss_sum": 0.0, "rows": 0, "correct": 0, "abs_err_sum": 0.0}
+        ev = self._eval_buffers()
+        for lo in range(0, n, self.R):
+            self._eval_chunk(X, Y, labels, lo, min(n, lo + self.R), loss=self.loss_kind,
+                             metrics=ev["metrics"], accumulate=lo > 0, ws=ev["ws"])
+        self.synchronize()      # (also check_device_errors, as loss() does)
+        m = ev["metrics"].tolist()
+        return {"loss_sum": float(m[0]), "rows": int(m[3]), "correct": int(m[1]),
+                "abs_err_sum": float(m[2])}
 
     def loss(self) -> float:
         """Local (this rank's) mean loss of the last step (host sync)."""

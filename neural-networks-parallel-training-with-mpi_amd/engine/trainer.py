@@ -69,6 +69,9 @@ class TrainResult:
     # (also under schedule["grad_norms"] / ["clip_coefs"], which travels with the rank results)
     grad_norms: List[float] = field(default_factory=list)
     clip_coefs: List[float] = field(default_factory=list)
+    # --val_metrics: global, per epoch -- accuracy under cross-entropy, mean absolute error under MSE
+    val_accs: List[float] = field(default_factory=list)
+    val_maes: List[float] = field(default_factory=list)
 
 
 def dist_train(args) -> Optional[TrainResult]:
@@ -581,7 +584,32 @@ def _run(j: Job) -> TrainResult:
                 gl = float(t[0] / max(t[1], 1.0))
                 res.global_losses.append(gl)
                 _print(cfg, rank, f"global loss: {gl}") if rank == 0 else None
-            if cfg.val_fraction > 0:
+            val_extra = {}
+            if cfg.val_fraction > 0 and cfg.val_metrics:
+                # the forward-only head: loss, hits and absolute error summed on the device, one
+                # host synchronisation; the four sums travel in one float64 all-reduce
+                vm = (eng.evaluate_metrics(Xv.to(dtype), Yv, Lv) if Xv is not None else
+                      {"loss_sum": 0.0, "rows": 0, "correct": 0, "abs_err_sum": 0.0})
+                full_loaded = False          # evaluation reused the input buffers
+                per = cfg.widths[-1] if cfg.loss == "mse" else 1
+                t = torch.tensor([vm["loss_sum"], float(vm["rows"]), float(vm["correct"]),
+                                  vm["abs_err_sum"]], dtype=torch.float64)
+                if world > 1:
+                    j.pg.allreduce_cpu(t)
+                vl = float(t[0] / max(float(t[1]) * per, 1.0))
+                res.val_losses.append(vl)
+                _print(cfg, rank, f"validation loss: {vl}") if rank == 0 else None
+                if cfg.loss == "xent":
+                    va = float(t[2] / max(float(t[1]), 1.0))
+                    res.val_accs.append(va)
+                    val_extra = {"val_acc": va}
+                    _print(cfg, rank, f"validation accuracy: {va}") if rank == 0 else None
+                else:
+                    vmae = float(t[3] / max(float(t[1]) * per, 1.0))
+                    res.val_maes.append(vmae)
+                    val_extra = {"val_mae": vmae}
+                    _print(cfg, rank, f"validation mae: {vmae}") if rank == 0 else None
+            elif cfg.val_fraction > 0:
                 vs, vn = eng.evaluate(Xv.to(dtype), Yv, Lv) if Xv is not None else (0.0, 0)
                 full_loaded = False          # evaluation reused the input buffers
                 per = cfg.widths[-1] if cfg.loss == "mse" else 1
@@ -599,7 +627,7 @@ def _run(j: Job) -> TrainResult:
                           parallel_efficiency=parallel_efficiency(sps, world,
                                                                   cfg.ref_samples_per_s),
                           **cvol, val_loss=res.val_losses[-1] if res.val_losses else None,
-                          **clip_metrics())
+                          **val_extra, **clip_metrics())
             if cfg.checkpoint and cfg.checkpoint_every and (epoch + 1) % cfg.checkpoint_every == 0:
                 _gather_state(eng, sync)
                 if rank == 0:

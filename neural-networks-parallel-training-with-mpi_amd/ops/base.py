@@ -41,6 +41,22 @@ class OpSet:
         the coefficient into ``clip_state`` ([max_norm, base_gs, last_norm, last_coef])."""
         raise NotImplementedError(f"{type(self).__name__}: clip_finalize is not supported")
 
+    # ---- forward-only output layer (csrc/kernels/head_eval.hip; TorchOps is the oracle) ----
+    def head_eval(self, a, W, b, y=None, labels=None, loss=None, logits_out=None, pred_out=None,
+                  metrics=None, accumulate: bool = False, ws=None):
+        """Logits ``a @ W^T + b`` of the output layer, without any gradient.  ``loss``: ``"mse"``
+        (targets ``y`` [rows, out]), ``"xent"`` (``labels`` [rows] int64, only compared with the
+        output index: an out-of-range label counts as a wrong row) or None (no target is read).
+        Optional outputs: ``logits_out`` (fp32, rows x >= out, row stride >= out), ``pred_out``
+        (int32 [rows], ``torch.argmax``'s rule: first maximum, a NaN is the maximum) and
+        ``metrics`` (float64 [4] = loss_sum, correct, abs_err_sum, rows; per-row fp32 values
+        summed in float64; ``accumulate``: added to instead of overwritten; the slot the loss
+        does not define is 0).  ``ws``: ``head_eval_workspace_bytes`` (with ``metrics``)."""
+        raise NotImplementedError(f"{type(self).__name__}: head_eval is not supported")
+
+    def head_eval_workspace_bytes(self, rows, in_f, out_f) -> int:
+        return 0
+
     def rowband_ok(self, rows, widths, act, loss) -> bool:
         """The whole forward + head + activation-gradient chain runs as one launch per step
         (see rowband.hip)."""

@@ -203,6 +203,49 @@ class HipOps(OpSet):
                             _p(wws), _p(lp), parts, float(loss_scale), _p(loss_out), self.stream,
                             sgd)
 
+    # ---------------- forward-only head (head_eval.hip) ----------------
+    def head_eval_workspace_bytes(self, rows, in_f, out_f) -> int:
+        return int(self.lib.head_eval_workspace_bytes(int(rows), int(in_f), int(out_f)))
+
+    def head_eval(self, a, W, b, y=None, labels=None, loss=None, logits_out=None, pred_out=None,
+                  metrics=None, accumulate: bool = False, ws=None):
+        """See OpSet.head_eval.  One launch (+ a one-block finalize with ``metrics``); what the
+        kernel does not take raises before anything is launched."""
+        rows, in_f = a.shape
+        out_f = W.shape[0]
+        _check(loss in (None, "mse", "xent"), f"head_eval: unknown loss {loss!r}")
+        _check(a.dtype in (torch.bfloat16, torch.float32) and a.stride(1) == 1,
+               "head_eval: bf16 / fp32 rows")
+        _check(W.dtype == torch.float32 and W.is_contiguous() and W.shape[1] == in_f and
+               b.dtype == torch.float32 and b.numel() == out_f and b.is_contiguous(),
+               "head_eval: dense fp32 [out, in] weights and [out] bias")
+        if loss == "mse":
+            _check(y is not None and y.dtype == torch.float32 and y.is_contiguous() and
+                   y.numel() >= rows * out_f, "head_eval: dense fp32 targets [rows, out]")
+        if loss == "xent":
+            _check(labels is not None and labels.dtype == torch.int64 and labels.is_contiguous()
+                   and labels.numel() >= rows, "head_eval: int64 labels [rows]")
+        ldl = 0
+        if logits_out is not None:
+            _check(logits_out.dtype == torch.float32 and logits_out.dim() == 2 and
+                   logits_out.shape[0] >= rows and logits_out.shape[1] >= out_f and
+                   logits_out.stride(1) == 1, "head_eval: fp32 logits [rows, >= out]")
+            ldl = logits_out.stride(0) if logits_out.shape[0] > 1 else max(logits_out.stride(0), out_f)
+        if pred_out is not None:
+            _check(pred_out.dtype == torch.int32 and pred_out.is_contiguous() and
+                   pred_out.numel() >= rows, "head_eval: int32 predictions [rows]")
+        if metrics is not None:
+            _check(metrics.dtype == torch.float64 and metrics.is_contiguous() and
+                   metrics.numel() >= 4, "head_eval: float64 metrics [4]")
+            self._check_ws(ws, self.head_eval_workspace_bytes(rows, in_f, out_f), "head_eval")
+        lda = a.stride(0) if rows > 1 else max(a.stride(0), in_f)
+        self.lib.head_eval(_p(a), 1 if a.dtype == torch.bfloat16 else 0, lda, rows, in_f, _p(W),
+                           _p(b), out_f, _p(y) if loss == "mse" else 0,
+                           _p(labels) if loss == "xent" else 0,
+                           -1 if loss is None else LOSS_CODES[loss], _p(logits_out), ldl,
+                           _p(pred_out), _p(metrics), int(bool(accumulate)),
+                           _p(ws) if metrics is not None else 0, self.stream)
+
     # ---------------- grouped backward (bf16) ----------------
     def head_deferred(self, a, W, b, y, inv_count: float, act_prev: str, dz_out, gW, gb, loss_out,
                       loss_scale: float, ws, sgd=None, labels=None, loss: str = "mse",

@@ -82,6 +82,42 @@ class TorchOps(OpSet):
         if dz_out is not None:
             dz_out.copy_(dl.mm(W.float()) * act_bwd_from_out(af, act_prev))
 
+    def head_eval(self, a, W, b, y=None, labels=None, loss=None, logits_out=None, pred_out=None,
+                  metrics=None, accumulate: bool = False, ws=None):
+        """The contract of OpSet.head_eval in plain torch (CPU path and the kernel's oracle)."""
+        rows, out_f = a.shape[0], W.shape[0]
+        if loss not in (None, "mse", "xent"):
+            raise ValueError(f"head_eval: unknown loss {loss!r}")
+        if (loss == "mse" and y is None) or (loss == "xent" and labels is None):
+            raise ValueError(f"head_eval: loss {loss!r} needs its targets")
+        with torch.no_grad():
+            logits = torch.addmm(b.float(), a.float(), W.float().t())
+            pred = (torch.argmax(logits, dim=1) if rows else
+                    torch.zeros(0, dtype=torch.int64, device=logits.device))
+            if logits_out is not None:
+                logits_out[:rows, :out_f].copy_(logits)
+            if pred_out is not None:
+                pred_out[:rows].copy_(pred)
+            if metrics is None:
+                return
+            vals = torch.zeros(4, dtype=torch.float64, device=metrics.device)
+            vals[3] = rows
+            if loss == "xent" and rows:
+                lab = labels.view(-1)
+                ok = (lab >= 0) & (lab < out_f)
+                zl = logits.gather(1, lab.clamp(0, out_f - 1).view(-1, 1)).squeeze(1)
+                zl = torch.where(ok, zl, torch.zeros_like(zl))
+                vals[0] = (torch.logsumexp(logits, dim=1) - zl).double().sum()
+                vals[1] = (pred == lab).sum()
+            elif loss == "mse" and rows:
+                d = logits - y.float().reshape(rows, out_f)
+                vals[0] = (d * d).sum(1).double().sum()
+                vals[2] = d.abs().sum(1).double().sum()
+            if accumulate:
+                metrics.add_(vals)
+            else:
+                metrics.copy_(vals)
+
     def gather_rows(self, src, idx, dst):
         dst[:idx.numel()].copy_(src.index_select(0, idx))
 

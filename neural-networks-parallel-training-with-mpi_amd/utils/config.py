@@ -70,6 +70,7 @@ class TrainConfig:
     averaging: str = "unweighted"     # unweighted (reference, D5) | weighted
     shuffle: bool = True
     val_fraction: float = 0.0         # held-out tail of every shard, evaluated after each epoch
+    val_metrics: bool = False         # also report validation accuracy (xent) / MAE (mse)
     grad_accum: int = 1               # micro-batches per optimizer step (gradient accumulation)
     # --- runtime ---
     seed: int = 0                     # init seed (reference: torch.manual_seed(0) on rank 0)
@@ -162,6 +163,10 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--val_fraction", type=float, default=0.0,
                    help="hold out this fraction of every rank's rows and print the global "
                         "validation loss after each epoch (the reference's dead x_val/y_val hook)")
+    p.add_argument("--val_metrics", action="store_true",
+                   help="with --val_fraction: also print the global validation accuracy "
+                        "(cross-entropy) or mean absolute error (MSE) after each epoch, from the "
+                        "forward-only evaluation head (one host synchronisation per evaluation)")
     p.add_argument("--grad_accum", "--accum_steps", dest="grad_accum", type=int, default=1,
                    help="micro-batches whose gradients are summed before one synchronisation + "
                         "optimizer step (with the whole-shard batch the shard is cut into this "
@@ -295,5 +300,7 @@ def validate(cfg: TrainConfig) -> None:
         raise ValueError("n_samples must be positive")
     if not 0.0 <= cfg.val_fraction < 1.0:
         raise ValueError("val_fraction must be in [0, 1)")
+    if cfg.val_metrics and not cfg.val_fraction > 0:
+        raise ValueError("--val_metrics needs --val_fraction > 0 (there are no validation rows)")
     if int(cfg.grad_accum) < 1:
         raise ValueError("grad_accum must be >= 1")
