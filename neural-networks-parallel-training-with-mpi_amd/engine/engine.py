@@ -99,7 +99,6 @@ class MLPEngine:
         self.device = torch.device(device)
         self.dtype = dtype
         self.R = max(1, int(rows_capacity))
-        self.nesterov = bool(nesterov)
         self.is_cuda = self.device.type == "cuda"
         L = self.L = spec.n_layers
         w = spec.widths
@@ -134,7 +133,7 @@ class MLPEngine:
         # every update site goes through this object (engine/optimizer.py)
         if clip_grad_norm is not None and not float(clip_grad_norm) > 0:    # (also NaN)
             raise ValueError(f"clip_grad_norm must be > 0, got {clip_grad_norm}")
-        self.opt = make_optimizer(optimizer, ops, arena, self.hp, self.nesterov,
+        self.opt = make_optimizer(optimizer, ops, arena, self.hp, nesterov,
                                   clip_grad_norm=clip_grad_norm)
         # Adam cannot ride in the kernels' fused epilogues (SgdFuse: one state buffer, the SGD
         # formula): every schedule runs in its unfused form, the update a separate pass.  So
@@ -203,9 +202,8 @@ class MLPEngine:
         self._rb_split: Dict[int, bool] = {}
         # the per-bucket collectives and updates of the comm-overlapped bodies
         self.pipe = BucketPipeline(
-            spec, arena, ops, sync, self.hp, self.nesterov, self.stream, bf16=bf16,
-            grad16=sync.update_grad() if self.comm_overlap else None, defer=not self.rb_overlap,
-            opt=self.opt)
+            spec, arena, ops, sync, self.opt, self.stream, bf16=bf16,
+            grad16=sync.update_grad() if self.comm_overlap else None, defer=not self.rb_overlap)
         self.rows = 0
         self._steps = 0
         self._graphs: Dict[tuple, object] = {}
@@ -305,6 +303,14 @@ class MLPEngine:
                 self.labels[:n].copy_(labels, non_blocking=True)
         self.rows = n
 
+    def _load_rows(self, X, Y, labels, lo: int, hi: int):
+        """load_batch of rows lo:hi of X and of whichever targets are given."""
+        self.load_batch(X[lo:hi], *(t if t is None else t[lo:hi] for t in (Y, labels)))
+
+    def _row_chunks(self, n: int):
+        """(lo, hi) of the row-capacity chunks of n rows, in order."""
+        return ((lo, min(n, lo + self.R)) for lo in range(0, n, self.R))
+
     def load_batch_indexed(self, X: torch.Tensor, Y: Optional[torch.Tensor],
                            labels: Optional[torch.Tensor], idx: torch.Tensor):
         """Mini-batch ``idx`` (int64, on the engine's device) of a resident shard, gathered
@@ -338,8 +344,7 @@ class MLPEngine:
                 self.loss_out.zero_()
                 ar.grad.zero_()
             else:
-                fz = (ops.sgd_fusion(ar, self.hp, self.nesterov, self._first)
-                      if self.tiny_fused else None)
+                fz = self.opt.fusion(self._first) if self.tiny_fused else None
                 ops.tiny_step(self.spec, ar, self.X[:rows], *self._targets(rows), self.inv_count,
                               self.loss_out, self.ws, sgd=fz, loss_scale=self.loss_scale)
             for i in reversed(range(L)):
@@ -526,7 +531,7 @@ class MLPEngine:
     # optimizer pass).  dgrad_i runs BEFORE wgrad_i here: it is the last reader of W_i.
     def _step_fused(self, first: bool):
         rows, ops, ar, L = self.rows, self.ops, self.arena, self.L
-        fz = ops.sgd_fusion(ar, self.hp, self.nesterov, first)
+        fz = self.opt.fusion(first)
         x = self.X[:rows]
         h = self._forward(x)
         self._mark("fwd")
@@ -659,8 +664,7 @@ class MLPEngine:
         self.images.mark(self.images.views is not None)
 
     def _step_rowband(self, first: bool):
-        fz = (self.ops.sgd_fusion(self.arena, self.hp, self.nesterov, first)
-              if self.fuse_sgd else None)
+        fz = self.opt.fusion(first) if self.fuse_sgd else None
         self._rb_launch(sgd=fz)
         # the fused combine rewrote the images from the updated weights; of the multi-rank
         # updates below only the inline tail's optimizer pass does
@@ -680,7 +684,7 @@ class MLPEngine:
     # of the group reads (dgrad_i reads W_i); the two slab workspaces alternate.
     def _step_grouped(self, first: bool):
         rows, ops, ar, L, main, pipe = self.rows, self.ops, self.arena, self.L, self.stream, self.pipe
-        fz = ops.sgd_fusion(ar, self.hp, self.nesterov, first) if self.fuse_sgd else None
+        fz = self.opt.fusion(first) if self.fuse_sgd else None
         comm = self.comm_overlap
         if comm:
             # several ranks, per-bucket collectives: each combine's finished layer gradient goes
@@ -1003,10 +1007,8 @@ class MLPEngine:
             self._eval_gw = torch.zeros_like(self.arena.grad_weight(last))
             self._eval_gb = torch.zeros_like(self.arena.grad_bias(last))
         total = 0.0
-        for lo in range(0, n, self.R):
-            hi = min(n, lo + self.R)
-            self.load_batch(X[lo:hi], Y[lo:hi] if Y is not None else None,
-                            labels[lo:hi] if labels is not None else None)
+        for lo, hi in self._row_chunks(n):
+            self._load_rows(X, Y, labels, lo, hi)
             rows = self.rows
             with self._on_stream(), torch.no_grad():
                 if self.use_tiny:
@@ -1048,8 +1050,7 @@ class MLPEngine:
     def _eval_chunk(self, X, Y, labels, lo: int, hi: int, loss=None, **outputs):
         """Rows lo..hi through the hidden layers and the forward-only head (on the stream);
         ``loss``: the loss whose targets (loaded with the rows) the head reads, None: neither."""
-        self.load_batch(X[lo:hi], Y[lo:hi] if Y is not None else None,
-                        labels[lo:hi] if labels is not None else None)
+        self._load_rows(X, Y, labels, lo, hi)
         rows, last = self.rows, self.L - 1
         y, lab = self._targets(rows) if loss is not None else (None, None)
         with self._on_stream(), torch.no_grad():
@@ -1069,8 +1070,7 @@ class MLPEngine:
         if n == 0:
             return res
         ev = self._eval_buffers()
-        for lo in range(0, n, self.R):
-            hi = min(n, lo + self.R)
+        for lo, hi in self._row_chunks(n):
             rows = hi - lo
             if classes:
                 self._eval_chunk(X, None, None, lo, hi, pred_out=ev["pred"][:rows])
@@ -1092,8 +1092,8 @@ class MLPEngine:
         if n == 0:
             return {"loss_sum": 0.0, "rows": 0, "correct": 0, "abs_err_sum": 0.0}
         ev = self._eval_buffers()
-        for lo in range(0, n, self.R):
-            self._eval_chunk(X, Y, labels, lo, min(n, lo + self.R), loss=self.loss_kind,
+        for lo, hi in self._row_chunks(n):
+            self._eval_chunk(X, Y, labels, lo, hi, loss=self.loss_kind,
                              metrics=ev["metrics"], accumulate=lo > 0, ws=ev["ws"])
         self.synchronize()      # (also check_device_errors, as loss() does)
         m = ev["metrics"].tolist()

@@ -3,9 +3,12 @@
 The update is issued from five places -- the inline tail, the per-layer passes behind the fused
 schedules, the bucket pipeline, the ZeRO-1 owner update and (SGD only) the deferred weight-gradient
 epilogue.  They all hold one of these objects and call :meth:`apply`; which formula runs, which
-state buffers exist and whether a step counter has to advance is decided here alone.
+state buffers exist and whether a step counter has to advance is decided here alone.  So are the
+operands: the object holds the op set, the arena, the hyper-parameter tensor and the formula's
+flags, and no site passes any of them -- a kernel that applies the update itself (the fused
+combines, the tiny step, the deferred epilogue) gets its operand tuple from :meth:`Sgd.fusion`.
 
-* :class:`Sgd` -- ``ops.sgd`` with the arguments the sites passed before this module existed.
+* :class:`Sgd` -- ``ops.sgd``, and ``ops.sgd_fusion`` for the kernels' fused epilogues.
 * :class:`Adam` -- ``ops.adam`` (torch.optim.Adam, or AdamW when ``decoupled``).  It cannot ride
   in the fused epilogues (SgdFuse carries one state buffer and the SGD formula), so the engine
   takes the unfused form of every schedule under it.  Its step number lives on the device:
@@ -114,16 +117,13 @@ class Sgd(_Clipped):
 
     def apply(self, first: bool, offset: int = 0, numel: Optional[int] = None,
               zero_grad: bool = True, grad_bf16=None, images=None):
-        kw = {}
-        if offset or numel is not None:
-            kw.update(offset=offset, numel=numel)
-        if not zero_grad:
-            kw["zero_grad"] = False
-        if grad_bf16 is not None:
-            kw["grad_bf16"] = grad_bf16
-        if images is not None:
-            kw["images"] = images
-        self.ops.sgd(self.arena, self.hp, self.nesterov, first, **kw)
+        self.ops.sgd(self.arena, self.hp, self.nesterov, first, zero_grad=zero_grad,
+                     offset=offset, numel=numel, grad_bf16=grad_bf16, images=images)
+
+    def fusion(self, first: bool, offset: int = 0):
+        """The SgdFuse operands of a kernel that applies this update itself (``offset``: to the
+        arena elements from there on -- the deferred weight-gradient epilogue)."""
+        return self.ops.sgd_fusion(self.arena, self.hp, self.nesterov, first, offset)
 
     def tick(self):
         """SGD has no step number: nothing is launched."""
@@ -153,6 +153,9 @@ class Adam(_Clipped):
         # (``first`` is SGD's momentum initialisation; Adam starts from zero state)
         self.ops.adam(self.arena, self.hp, self.t, self.decoupled, zero_grad=zero_grad,
                       offset=offset, numel=numel, grad_bf16=grad_bf16, images=images)
+
+    def fusion(self, first: bool, offset: int = 0):
+        raise RuntimeError("Adam has no fused epilogue (fusable is False): nothing may ask")
 
     def tick(self):
         self.ops.adam_tick(self.hp, self.t)

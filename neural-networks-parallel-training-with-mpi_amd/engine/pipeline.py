@@ -21,19 +21,16 @@ from typing import Dict, List, Optional, Tuple
 
 import torch
 from ..utils.knobs import knob
-from .optimizer import Sgd
 
 
 class BucketPipeline:
-    def __init__(self, spec, arena, ops, sync, hp, nesterov: bool, stream, *, grad16, bf16: bool,
-                 defer: bool, opt=None):
-        """``grad16``: the bf16 payload the per-bucket updates read (None: the fp32 gradient);
+    def __init__(self, spec, arena, ops, sync, opt, stream, *, grad16, bf16: bool, defer: bool):
+        """``opt``: the optimizer every update goes through (engine/optimizer.py);
+        ``grad16``: the bf16 payload the per-bucket updates read (None: the fp32 gradient);
         ``bf16``: bf16 compute; ``defer``: the schedule launches the chunk weight gradients that
-        can carry deferred updates; ``opt``: the optimizer every update goes through
-        (engine/optimizer.py; default: SGD-momentum over ``hp``)."""
+        can carry deferred updates."""
         self.spec, self.arena, self.ops, self.sync = spec, arena, ops, sync
-        self.hp, self.nesterov, self.stream = hp, nesterov, stream
-        self.opt = opt if opt is not None else Sgd(ops, arena, hp, nesterov)
+        self.opt, self.stream = opt, stream
         self.sharded = sync.sharded
         # ev_wfree[l]: the last reader of layer l's weights has been issued
         self.ev_wfree = ([torch.cuda.Event(enable_timing=False) for _ in range(spec.n_layers)]
@@ -95,7 +92,7 @@ class BucketPipeline:
         """Optimizer update of the whole arena (or, sharded, of this rank's slice + gathers)."""
         if self.sharded:
             # (its clip follows the reduce-scatter, inside update())
-            self.sync.update(self.ops, self.hp, self.nesterov, first, opt=self.opt)
+            self.sync.update(self.opt, first)
         else:
             self.opt.clip()        # (clipping off: launches nothing)
             self.opt.apply(first)
@@ -178,7 +175,7 @@ class BucketPipeline:
             main.wait_event(self.ev_ar[part.index])      # the partner's all-reduce has completed
         woff = ar.by_name[f"layers.{2 * (i + 1)}.weight"].offset + part.rows[0] * in_f
         self.ops.linear_wgrad_defer(dz, x_in, ar.weight(i, g16)[r0:r1], ar.bias(i, g16)[r0:r1],
-                                    ar, self.hp, self.nesterov, self.first, woff, g16)
+                                    ar, woff, g16, self.opt.fusion(self.first, offset=woff))
         # the rest of the partner bucket (its layer's bias and padding, in the last chunk)
         wend = woff + (r1 - r0) * in_f
         rest = part.offset + part.numel - wend

@@ -85,10 +85,13 @@ class HipOps(OpSet):
         return epilogue or bool(self.lib.wgrad_will_split(out_f, in_f, rows))
 
     @staticmethod
-    def sgd_fusion(arena, hp, nesterov: bool, first: bool):
-        sh = _p(arena.shadow) if arena.shadow is not None else 0
-        return (_p(arena.grad), _p(arena.master), _p(arena.momentum), sh, _p(hp), int(nesterov),
-                int(first))
+    def sgd_fusion(arena, hp, nesterov: bool, first: bool, offset: int = 0):
+        """The SgdFuse operands (kernels.h) of an update applied to the arena from element
+        ``offset`` on: the only place the tuple is built."""
+        e, o = 4, offset     # bytes per fp32 element
+        sh = _p(arena.shadow) + 2 * o if arena.shadow is not None else 0
+        return (_p(arena.grad) + e * o, _p(arena.master) + e * o, _p(arena.momentum) + e * o, sh,
+                _p(hp), int(nesterov), int(first))
 
     def wgrad_can_write_bf16(self, rows, out_f, in_f) -> bool:
         """True when the (un-split) weight gradient can store bf16 gradients itself."""
@@ -281,11 +284,11 @@ class HipOps(OpSet):
     def wgrad_defer_ok(self, rows, out_f, in_f) -> bool:
         return bool(self.lib.wgrad_defer_ok(out_f, in_f, rows))
 
-    def linear_wgrad_defer(self, dz, x, gW16, gb16, arena, hp, nesterov: bool, first: bool,
-                           other_offset: int, g16):
+    def linear_wgrad_defer(self, dz, x, gW16, gb16, arena, other_offset: int, g16, sgd):
         """Weight gradient ``dz^T x`` stored as bf16 into (gW16, gb16) -- the all-reduce payload --
         while its epilogue applies SGD-momentum to the arena weights at ``other_offset`` (a region
-        of the same [out, in] shape whose reduced bf16 gradient is in ``g16`` at that offset)."""
+        of the same [out, in] shape whose reduced bf16 gradient is in ``g16`` at that offset).
+        ``sgd``: the update's operands at that offset (``sgd_fusion(..., offset=other_offset)``)."""
         rows, M = dz.shape
         N = x.shape[1]
         _check(self.wgrad_defer_ok(rows, M, N), "deferred update: weight gradient not eligible")
@@ -293,13 +296,9 @@ class HipOps(OpSet):
                "deferred update: dense bf16 outputs")
         _check(other_offset + M * N <= arena.numel and g16.numel() >= other_offset + M * N,
                "deferred update: region out of range")
-        e, o = 4, other_offset
-        sh = _p(arena.shadow) + 2 * o if arena.shadow is not None else 0
-        other = (_p(arena.grad) + e * o, _p(arena.master) + e * o, _p(arena.momentum) + e * o, sh,
-                 _p(hp), int(nesterov), int(first))
         self.lib.linear_wgrad_bf16_out16_defer(_p(dz), dz.stride(0), _p(x), x.stride(0), _p(gW16),
-                                               _p(gb16), M, N, rows, other, _p(g16) + 2 * o,
-                                               self.stream)
+                                               _p(gb16), M, N, rows, sgd,
+                                               _p(g16) + 2 * other_offset, self.stream)
 
     # ---- wide-model backward pairs (one launch: weight gradient + SGD beside a dgrad) -------
     def wide_pair_wgrad_ok(self, rows, out_f, in_f) -> bool:

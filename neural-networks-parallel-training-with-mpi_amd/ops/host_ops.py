@@ -38,9 +38,10 @@ class HostOps(TorchOps):
     tiny_supported = can_fuse_sgd = tiny_can_fuse_sgd = yes   # (see OpSet)
 
     @staticmethod
-    def sgd_fusion(arena, hp, nesterov: bool, first: bool):
-        return (_p(arena.grad), _p(arena.master), _p(arena.momentum), 0, _p(hp), int(nesterov),
-                int(first))
+    def sgd_fusion(arena, hp, nesterov: bool, first: bool, offset: int = 0):
+        e, o = 4, offset     # bytes per fp32 element; the CPU arena has no shadow
+        return (_p(arena.grad) + e * o, _p(arena.master) + e * o, _p(arena.momentum) + e * o, 0,
+                _p(hp), int(nesterov), int(first))
 
     def tiny_step(self, spec, arena, X, y, labels, inv_count, loss_out, ws, sgd=None,
                   loss_scale=None):

@@ -122,7 +122,8 @@ class TorchOps(OpSet):
         dst[:idx.numel()].copy_(src.index_select(0, idx))
 
     def sgd(self, arena, hp, nesterov: bool, first: bool, zero_grad: bool = True, offset: int = 0,
-            numel: int = None, grad_bf16=None):
+            numel: int = None, grad_bf16=None, images=None):
+        # (``images``: ignored -- the row-band weight images are a HIP path, there are none here)
         lr, mom, damp, wd, gs = [float(v) for v in hp.tolist()[:5]]
         n = arena.numel - offset if numel is None else numel
         sl = slice(offset, offset + n)

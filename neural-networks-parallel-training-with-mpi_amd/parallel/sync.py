@@ -165,25 +165,25 @@ class TorchDistSync(GradSync):
         if self.bf16:
             view.copy_(view.to(torch.bfloat16))
             self._rounded.append(view)
+        w = self._reduce(view, async_op=self.overlap)
+        if w is not None:
+            self._works.append(w)
+
+    def _reduce(self, view, async_op: bool = False):
+        """The collectives that reduce ``view``; the work handle of an asynchronous one."""
         if self.mode == "root":
             # reference pattern: everything through rank 0 (reduce to root, then fan out)
             dist.reduce(view, dst=0, group=self.group)
             dist.broadcast(view, src=0, group=self.group)
-            return
-        w = dist.all_reduce(view, group=self.group, async_op=self.overlap)
-        if w is not None:
-            self._works.append(w)
+            return None
+        return dist.all_reduce(view, group=self.group, async_op=async_op)
 
     def comm_only(self):
         for b in self.arena.buckets:
             view = self.arena.grad[b.offset:b.offset + b.numel]
             if self.bf16:   # the payload the step sends (the wire-byte count assumes it)
                 view = view.to(torch.bfloat16)
-            if self.mode == "root":
-                dist.reduce(view, dst=0, group=self.group)
-                dist.broadcast(view, src=0, group=self.group)
-            else:
-                dist.all_reduce(view, group=self.group)
+            self._reduce(view)
 
     def finish(self):
         for w in self._works:
@@ -242,7 +242,6 @@ class NativeRcclSync(GradSync):
         self.gbuf = (torch.zeros(arena.numel, dtype=torch.bfloat16, device=arena.grad.device)
                      if self.bf16 else None)
         self._comm_stream = torch.cuda.ExternalStream(self.gs.comm_stream)
-        import os
         self.bf16_reduce = bf16_reduce or knob("NNMPI_BF16_REDUCE", "acc32")
         if self.bf16_reduce not in ("acc32", "rccl"):
             raise ValueError(f"bf16_reduce must be acc32 or rccl, not {self.bf16_reduce!r}")
@@ -278,33 +277,43 @@ class NativeRcclSync(GradSync):
         else:
             self.comm.allreduce(ptr, n, dt, 0, h)
 
+    def _payload(self, bucket, h: int, written=()):
+        """(pointer, dtype code) of the bucket's payload, ready to reduce on stream ``h``."""
+        if not self.bf16:
+            return self.arena.grad[bucket.offset:].data_ptr(), 0
+        # cast the fp32 gradient into the payload, except the `written` arena ranges whose
+        # bf16 values the producing kernels stored there themselves
+        for lo, hi in _subtract((bucket.offset, bucket.offset + bucket.numel), written):
+            self.native.lib().cast_f32_bf16(self.arena.grad[lo:].data_ptr(),
+                                            self.gbuf[lo:].data_ptr(), hi - lo, h)
+        return self.gbuf[bucket.offset:].data_ptr(), 1
+
+    def _cast_back(self, bucket, ptr: int, h: int):
+        self.native.lib().cast_bf16_f32(ptr, self.arena.grad[bucket.offset:].data_ptr(),
+                                        bucket.numel, h)
+
+    def _inline(self, bucket, h: int, written=()):
+        """The bucket's whole reduction on stream ``h``: payload, collective(s), back to fp32."""
+        ptr, dt = self._payload(bucket, h, written)
+        if self.mode == "root":
+            # reference pattern (ref.py:185-203): everything through rank 0
+            self.comm.reduce(ptr, bucket.numel, dt, 0, 0, h)
+            self.comm.broadcast(ptr, bucket.numel, dt, 0, h)
+        else:
+            self._allreduce(ptr, bucket.numel, dt, h)
+        if self.bf16:
+            self._cast_back(bucket, ptr, h)
+
     def _launch(self, bucket, stream=None, cast_back: bool = True, written=()):
-        view = self.arena.grad[bucket.offset:bucket.offset + bucket.numel]
         self.note(2 if self.mode == "root" else 1, bucket.index, bucket.offset, bucket.numel,
                   int(self.bf16))
         h = int(stream.cuda_stream) if stream is not None else self.native.stream_handle()
-        lib = self.native.lib()
-        ptr, dt = view.data_ptr(), 0
-        if self.bf16:
-            ptr, dt = self.gbuf[bucket.offset:].data_ptr(), 1
-            # cast the fp32 gradient into the payload, except the `written` arena ranges whose
-            # bf16 values the producing kernels stored there themselves
-            for lo, hi in _subtract((bucket.offset, bucket.offset + bucket.numel), written):
-                lib.cast_f32_bf16(self.arena.grad[lo:].data_ptr(), self.gbuf[lo:].data_ptr(),
-                                  hi - lo, h)
         if self.inline:
-            if self.mode == "root":
-                # reference pattern (ref.py:185-203): everything through rank 0
-                self.comm.reduce(ptr, bucket.numel, dt, 0, 0, h)
-                self.comm.broadcast(ptr, bucket.numel, dt, 0, h)
-            else:
-                self._allreduce(ptr, bucket.numel, dt, h)
-            if self.bf16:
-                lib.cast_bf16_f32(ptr, view.data_ptr(), bucket.numel, h)
-            return
+            return self._inline(bucket, h, written)
+        ptr, dt = self._payload(bucket, h, written)
         self.gs.bucket_ready(bucket.index, ptr, bucket.numel, dt, h)
         if self.bf16 and cast_back:   # back to fp32 on the comm stream, ahead of its update
-            lib.cast_bf16_f32(ptr, view.data_ptr(), bucket.numel, self.gs.comm_stream)
+            self._cast_back(bucket, ptr, self.gs.comm_stream)
         self._launched = True
 
     def update_grad(self):
@@ -327,20 +336,8 @@ class NativeRcclSync(GradSync):
 
     def comm_only(self):
         h = self.native.stream_handle()
-        lib = self.native.lib()
         for b in self.arena.buckets:
-            view = self.arena.grad[b.offset:b.offset + b.numel]
-            ptr, dt = view.data_ptr(), 0
-            if self.bf16:
-                ptr, dt = self.gbuf[b.offset:].data_ptr(), 1
-                lib.cast_f32_bf16(view.data_ptr(), ptr, b.numel, h)
-            if self.mode == "root":
-                self.comm.reduce(ptr, b.numel, dt, 0, 0, h)
-                self.comm.broadcast(ptr, b.numel, dt, 0, h)
-            else:
-                self._allreduce(ptr, b.numel, dt, h)
-            if self.bf16:
-                lib.cast_bf16_f32(ptr, view.data_ptr(), b.numel, h)
+            self._inline(b, h)      # (no note(): nothing is added to the collective signature)
 
     def finish(self):
         if self._launched:
@@ -428,26 +425,48 @@ class ShardedSync(GradSync):
     def _views(self, buf):
         return [buf[r * self.shard:(r + 1) * self.shard] for r in range(self.world)]
 
-    def _reduce_scatter(self, h: int):
+    def _handle(self):
+        """The current stream's handle for the RCCL calls (gloo: None)."""
+        return self.native.stream_handle() if self.comm is not None else None
+
+    def _reduce_scatter(self, h):
+        if self.comm is None:
+            # gloo has no reduce-scatter: all-reduce, this rank uses its slice (the same sums)
+            dist.all_reduce(self.arena.grad, group=self.group)
+            return
         g = self.arena.grad.data_ptr()
         if self.scratch32 is not None:
             self.comm.reduce_scatter_f32_ordered(g, self.scratch32.data_ptr(), self.shard, h)
         else:
             self.comm.reduce_scatter(g, g + 4 * self.off, self.shard, 0, 0, h)
 
-    def update(self, ops, hp, nesterov: bool, first: bool, opt=None):
-        """Reduce-scatter -> owner update -> all-gather, on the current (compute) stream.
-        ``opt``: the optimizer object (engine/optimizer.py) applied to the owner slice; default
-        SGD-momentum over ``hp``."""
+    def _gather_params(self, h, refresh_shadow: bool = True):
+        """All-gather the updated parameters.  RCCL: the bf16 shadow + the fp32 pieces the
+        kernels read, or without a shadow the fp32 master.  gloo: the master, and
+        (``refresh_shadow``) a local copy into the shadow where there is one."""
         ar = self.arena
-        if opt is None:
-            from ..engine.optimizer import Sgd
-            opt = Sgd(ops, ar, hp, nesterov)
+        if self.comm is None:
+            dist.all_gather(self._views(ar.master),
+                            ar.master[self.off:self.off + self.shard].clone(), group=self.group)
+            if refresh_shadow and ar.shadow is not None:
+                ar.shadow.copy_(ar.master)
+        elif ar.shadow is not None:
+            s = ar.shadow.data_ptr()
+            self.comm.allgather(s + 2 * self.off, s, self.shard, 1, h)
+            offs, cnts, roots = self.pieces
+            self.comm.broadcast_pieces(ar.master.data_ptr(), offs, cnts, roots, 0, h)
+        else:
+            m = ar.master.data_ptr()
+            self.comm.allgather(m + 4 * self.off, m, self.shard, 0, h)
+
+    def update(self, opt, first: bool):
+        """Reduce-scatter -> owner update -> all-gather, on the current (compute) stream.
+        ``opt``: the optimizer object (engine/optimizer.py) applied to the owner slice."""
         self._opt = opt
         self.note(3, 0, 0, self.shard, 0)
+        h = self._handle()
+        self._reduce_scatter(h)
         if self.comm is not None:
-            h = self.native.stream_handle()
-            self._reduce_scatter(h)
             # clipping: the sum of squares of this rank's reduced slice, then the P sums
             # all-gathered bitwise (a double travels as two fp32 words) on the same stream and
             # added in rank order -- every rank holds the same coefficient bit for bit
@@ -456,42 +475,15 @@ class ShardedSync(GradSync):
                 lambda buf: self.comm.allgather(buf.data_ptr() + 8 * self.rank, buf.data_ptr(),
                                                 2, 0, h)))
         else:
-            dist.all_reduce(ar.grad, group=self.group)
             # the full gradient is here: the norm the all-reduce path takes, no extra collective
             opt.clip()
         opt.apply(first, offset=self.off, numel=self.shard)
-        if self.comm is not None:
-            if ar.shadow is not None:
-                s = ar.shadow.data_ptr()
-                self.comm.allgather(s + 2 * self.off, s, self.shard, 1, h)
-                offs, cnts, roots = self.pieces
-                self.comm.broadcast_pieces(ar.master.data_ptr(), offs, cnts, roots, 0, h)
-            else:
-                m = ar.master.data_ptr()
-                self.comm.allgather(m + 4 * self.off, m, self.shard, 0, h)
-        else:
-            dist.all_gather(self._views(ar.master),
-                            ar.master[self.off:self.off + self.shard].clone(), group=self.group)
-            if ar.shadow is not None:
-                ar.shadow.copy_(ar.master)
+        self._gather_params(h)
 
     def comm_only(self):
-        ar = self.arena
-        if self.comm is None:
-            dist.all_reduce(ar.grad, group=self.group)
-            dist.all_gather(self._views(ar.master),
-                            ar.master[self.off:self.off + self.shard].clone(), group=self.group)
-            return
-        h = self.native.stream_handle()
+        h = self._handle()
         self._reduce_scatter(h)
-        if ar.shadow is not None:
-            s = ar.shadow.data_ptr()
-            self.comm.allgather(s + 2 * self.off, s, self.shard, 1, h)
-            offs, cnts, roots = self.pieces
-            self.comm.broadcast_pieces(ar.master.data_ptr(), offs, cnts, roots, 0, h)
-        else:
-            m = ar.master.data_ptr()
-            self.comm.allgather(m + 4 * self.off, m, self.shard, 0, h)
+        self._gather_params(h, refresh_shadow=False)
 
     def gather_state(self, state_buffers=None):
         """Full fp32 master + every optimizer state buffer on every rank (checkpoint / final
@@ -503,8 +495,7 @@ class ShardedSync(GradSync):
         for buf in [ar.master] + list(state_buffers):
             own = buf[self.off:self.off + self.shard]
             if self.comm is not None:
-                import torch as _t
-                s = _t.cuda.current_stream()
+                s = torch.cuda.current_stream()
                 p = buf.data_ptr()
                 self.comm.allgather(p + 4 * self.off, p, self.shard, 0, int(s.cuda_stream))
                 s.synchronize()
@@ -516,7 +507,6 @@ def shm_sync_ok(device_type: str, world: int, local_world: int, grad_dtype: str 
                 mode: str = "allreduce") -> bool:
     """CPU ranks that all run on this machine, fp32 all-reduce: the shared-memory transport
     applies (NNMPI_SHM=0 keeps gloo)."""
-    import os
     return (device_type == "cpu" and world > 1 and local_world == world and grad_dtype == "fp32"
             and mode == "allreduce" and knob("NNMPI_SHM", "1") != "0")
 

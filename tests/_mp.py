@@ -33,6 +33,24 @@ def run_ranks(cfg, world, fn_name="run_worker"):
         return [torch.load(os.path.join(d, f"r{r}.pt"), weights_only=True) for r in range(world)]
 
 
+def _fn_entry(rank, world, port, fn, args, outdir):
+    os.environ.update({"RANK": str(rank), "WORLD_SIZE": str(world), "LOCAL_RANK": str(rank),
+                       "LOCAL_WORLD_SIZE": str(world), "MASTER_ADDR": "127.0.0.1",
+                       "MASTER_PORT": str(port)})
+    torch.set_num_threads(1)
+    torch.save(fn(rank, world, *args), os.path.join(outdir, f"r{rank}.pt"))
+
+
+def run_fn(fn, world, *args):
+    """``fn(rank, world, *args)`` (a module-level function) on ``world`` spawned ranks with the
+    launcher environment of :func:`run_ranks` set; every rank's return value (plain containers:
+    it travels through ``torch.save`` / ``weights_only`` loading)."""
+    with tempfile.TemporaryDirectory() as d:
+        mp.start_processes(_fn_entry, args=(world, _free_port(), fn, args, d), nprocs=world,
+                           join=True, start_method="spawn")
+        return [torch.load(os.path.join(d, f"r{r}.pt"), weights_only=True) for r in range(world)]
+
+
 def run_ranks_proc(cfg: dict, world: int, env_per_rank=None, timeout: float = 150.0,
                    entry: str = "_rank_entry.py"):
     """Like :func:`run_ranks`, but every rank is an independent ``subprocess`` (as mpiexec /

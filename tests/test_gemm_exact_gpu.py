@@ -592,8 +592,8 @@ def test_wgrad_deferred_update():
     a1.bias(0, g16).copy_(sent.expand(H))
     g16_before = g16.clone()
     hp = torch.tensor([0.01, 0.9, 0.0, 1e-2, 0.5, 0, 0, 0], device=DEV)
-    ops.linear_wgrad_defer(_put(dz, True), _put(x, True), a1.weight(0, g16), a1.bias(0, g16), a1, hp,
-                           False, False, other.offset, g16)
+    ops.linear_wgrad_defer(_put(dz, True), _put(x, True), a1.weight(0, g16), a1.bias(0, g16), a1,
+                           other.offset, g16, ops.sgd_fusion(a1, hp, False, False, other.offset))
     torch.cuda.synchronize()
     _eq(a1.weight(0, g16), ex.bf16_rne(wW), "payload gW16")
     _eq(a1.bias(0, g16), ex.bf16_rne(wb), "payload gb16")

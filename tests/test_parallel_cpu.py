@@ -386,3 +386,92 @@ def test_row_chunk_buckets_cpu_bitwise(monkeypatch):
     monkeypatch.setenv("NNMPI_CHUNK_MIN_TILES", "2")
     ar = Arena([(512, 512), (512, 512), (1, 512)], "meta", bucket_bytes=0.25 * 2 ** 20)
     assert ar.layer_chunks == {0: 2, 1: 2}
+
+
+# --------------------------------------------------------------------------------------------
+# comm_only() issues the step's collectives (bench.py times it as "the collectives of one step")
+# --------------------------------------------------------------------------------------------
+SYNC_KINDS = ["allreduce", "root", "allreduce-bf16", "zero1"]
+
+
+def _sync_collectives(rank, world, kinds):
+    """On one gloo rank: {kind: [collectives of one step, collectives of comm_only()]} as
+    (torch.distributed function, elements sent) lists, for the 2-3-1 reference model.  The
+    recording covers engine.step() alone -- sync.begin() to the update; the loss reduction is the
+    trainer's and is not part of it."""
+    import torch.distributed as dist
+    from nnmpi_amd.engine.arena import Arena
+    from nnmpi_amd.engine.engine import MLPEngine
+    from nnmpi_amd.models.mlp import MLPSpec, reference_init
+    from nnmpi_amd.ops.torch_ops import TorchOps
+    from nnmpi_amd.parallel.sync import ShardedSync, TorchDistSync
+    dist.init_process_group("gloo", rank=rank, world_size=world)
+    calls = None
+    real = {n: getattr(dist, n) for n in ("all_reduce", "reduce", "broadcast", "all_gather")}
+
+    def recording(name):
+        def call(*a, **kw):
+            if calls is not None:
+                calls.append((name, int((a[1] if name == "all_gather" else a[0]).numel())))
+            return real[name](*a, **kw)
+        return call
+    for n in real:
+        setattr(dist, n, recording(n))
+    widths = [2, 3, 1]
+    spec = MLPSpec(tuple(widths), "relu", "mse")
+    out = {}
+    try:
+        for kind in kinds:
+            arena = Arena([spec.layer_shape(i) for i in range(spec.n_layers)], "cpu",
+                          bucket_bytes=256, pad_to=64 * world)
+            arena.bind_model(reference_init(widths))
+            # (the planner never closes a bucket below 64 KiB on its own: lift that here)
+            arena.buckets = arena._plan_buckets(256, 4, min_bytes=0)
+            if kind == "zero1":
+                sync = ShardedSync(arena, world, rank, group=None)
+            else:
+                mode, _, payload = kind.partition("-")
+                sync = TorchDistSync(arena, None, world, mode=mode, grad_dtype=payload or "fp32")
+                assert len(arena.buckets) == 2       # (one per layer: more than one sequence)
+            eng = MLPEngine(spec, arena, TorchOps("cpu"), sync, device="cpu", dtype=torch.float32,
+                            rows_capacity=4, lr=0.01, momentum=0.9)
+            g = torch.Generator().manual_seed(rank)
+            eng.load_batch(torch.randn(4, 2, generator=g), torch.randn(4, 1, generator=g))
+            eng.set_scales(0.25, 0.25, 1.0 / world)
+            eng.step()                               # (the first step initialises the momentum)
+            rec = []
+            for fn in (eng.step, sync.comm_only):
+                calls = []
+                fn()
+                rec.append([list(c) for c in calls])
+                calls = None
+            out[kind] = rec
+    finally:
+        for n, fn in real.items():
+            setattr(dist, n, fn)
+        dist.destroy_process_group()
+    return out
+
+
+@pytest.fixture(scope="module")
+def sync_collectives():
+    from _mp import run_fn
+    return run_fn(_sync_collectives, 2, SYNC_KINDS)
+
+
+@pytest.mark.parametrize("kind", SYNC_KINDS)
+def test_comm_only_issues_the_steps_collectives(sync_collectives, kind):
+    """TorchDistSync (all-reduce, the root pattern, the bf16 payload) and the gloo ShardedSync on
+    2 ranks: the (collective, elements) list of one step equals that of comm_only(), on every
+    rank -- and is what the sync is documented to issue."""
+    per_bucket = {"root": ["reduce", "broadcast"]}.get(kind, ["all_reduce"])
+    for rank, rec in enumerate(sync_collectives):
+        step, comm = rec[kind]
+        assert step == comm, (rank, step, comm)
+        names = [c[0] for c in step]
+        if kind == "zero1":
+            assert names == ["all_reduce", "all_gather"]
+            total, shard = step[0][1], step[1][1]
+            assert total == 2 * shard and total % 128 == 0
+        else:
+            assert names == per_bucket * 2

@@ -65,8 +65,8 @@ class _Recorder:
         eng.step = traced_step
 
 
-def _trace(cfg, grouped=None, empty_third=False):
-    """Run ``cfg`` eagerly with a recording engine; the per-step traces."""
+def _run_recorded(cfg, grouped=None):
+    """Run ``cfg`` eagerly with a recording engine; the recorder (its ``engine`` stays usable)."""
     import nnmpi_amd.engine.engine as eng_mod
     rec = _Recorder()
     orig = eng_mod.MLPEngine.__init__
@@ -82,6 +82,12 @@ def _trace(cfg, grouped=None, empty_third=False):
         trainer.run_worker(cfg)
     finally:
         eng_mod.MLPEngine.__init__ = orig
+    return rec
+
+
+def _trace(cfg, grouped=None, empty_third=False):
+    """The per-step traces of ``cfg``."""
+    rec = _run_recorded(cfg, grouped)
     if empty_third:
         eng = rec.engine
         eng.load_batch(eng.X[:0], eng.Y[:0])
@@ -172,3 +178,61 @@ def test_step_launch_trace(case, monkeypatch):
     else:
         assert steps[1] == EXPECTED[case]
         assert steps[2] == EXPECTED[case]
+
+
+# The communicator calls of the inline native sync: bench.py times ``comm_only()`` as "exactly the
+# collectives of one step", so both must put the same calls on the communicator.
+class _CommProxy:
+    """Forwards to the communicator and records (call, elements, dtype code) of its collectives
+    (dtype codes: 0 fp32, 1 bf16; the two scratch-buffer all-reduces have theirs in the name)."""
+    # call -> (position of the element count, position of the dtype code or the fixed code)
+    CALLS = {"allreduce": (1, 2), "reduce": (1, 2), "broadcast": (1, 2),
+             "allreduce_bf16_acc32": (2, None), "allreduce_f32_ordered": (2, None)}
+    FIXED = {"allreduce_bf16_acc32": 1, "allreduce_f32_ordered": 0}
+
+    def __init__(self, comm):
+        self._comm, self.calls = comm, []
+
+    def __getattr__(self, name):
+        fn = getattr(self._comm, name)
+        if name not in self.CALLS:
+            return fn
+        n_at, dt_at = self.CALLS[name]
+
+        def call(*a):
+            dt = self.FIXED[name] if dt_at is None else int(a[dt_at])
+            self.calls.append((name, int(a[n_at]), dt))
+            return fn(*a)
+        return call
+
+
+INLINE_SYNCS = {
+    "fp32": (dict(), lambda n: [("allreduce", n, 0)]),
+    "bf16": (dict(grad_dtype="bf16"), lambda n: [("allreduce_bf16_acc32", n, 1)]),
+    "root": (dict(sync="root"), lambda n: [("reduce", n, 0), ("broadcast", n, 0)]),
+}
+
+
+@pytest.mark.parametrize("kind", sorted(INLINE_SYNCS))
+def test_inline_sync_comm_only_issues_the_steps_collectives(kind):
+    """Inline NativeRcclSync over a 1-rank communicator (fp32 payload, bf16 payload, the root
+    pattern): the calls one eager step makes on the communicator equal those of comm_only() --
+    one sequence over the single whole-arena bucket -- and comm_only() leaves the collective
+    signature alone."""
+    kw, want = INLINE_SYNCS[kind]
+    rec = _run_recorded(_cfg(device="cuda", comm="native", comm_mode="inline", nepochs=2, **kw))
+    eng = rec.engine
+    sync = eng.sync
+    assert sync.inline and len(eng.arena.buckets) == 1
+    proxy = sync.comm = _CommProxy(sync.comm)
+    eng.step()
+    eng.synchronize()
+    step, proxy.calls = proxy.calls, []
+    seq, sig = sync.seq, sync.sig
+    with eng._on_stream():
+        sync.comm_only()
+    eng.synchronize()
+    print("COMM", json.dumps({kind: [step, proxy.calls]}))
+    assert step == proxy.calls
+    assert step == want(eng.arena.numel)
+    assert (sync.seq, sync.sig) == (seq, sig)

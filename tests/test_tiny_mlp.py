@@ -489,6 +489,33 @@ def test_sgd_fusion_needs_the_single_block_form():
         run_step("hip", c, sgd_hp=[0.1, 0.9, 0.0, 0.0, 1.0])
 
 
+def test_optimizer_fusion_is_the_op_sets_tuple():
+    """Sgd.fusion (engine/optimizer.py), the only source of the fused-update operands the
+    engine and the bucket pipeline use: entry for entry ops.sgd_fusion over the object's own
+    arena / hyper-parameters / nesterov flag; at an offset of 64 elements the three fp32 pointers
+    (gradient, master, momentum) advance by 4 * 64 bytes, the absent shadow stays 0 and the
+    hyper-parameter pointer and the flags stay."""
+    from nnmpi_amd.engine.optimizer import adam_hparams, make_optimizer, sgd_hparams
+    ops, dev = _ops("host")
+    _, arena = make_arena(random_case((2, 3, 1), "relu", "mse", 16, 0), dev)
+    assert arena.numel > 64
+    hp = sgd_hparams(0.1, 0.9, 0.0, 0.0, dev)
+    for nesterov in (False, True):
+        opt = make_optimizer("sgd", ops, arena, hp, nesterov)
+        for first in (True, False):
+            base = ops.sgd_fusion(arena, hp, nesterov, first)
+            assert opt.fusion(first) == base
+            assert base == (arena.grad.data_ptr(), arena.master.data_ptr(),
+                            arena.momentum.data_ptr(), 0, hp.data_ptr(), int(nesterov), int(first))
+            moved = opt.fusion(first, offset=64)
+            assert moved == ops.sgd_fusion(arena, hp, nesterov, first, 64)
+            assert [m - b for m, b in zip(moved, base)] == [4 * 64] * 3 + [0] * 4
+    adam = make_optimizer("adam", ops, arena, adam_hparams(0.1, 0.9, 0.999, 1e-8, 0.0, dev))
+    assert not adam.fusable
+    with pytest.raises(RuntimeError, match="fused"):
+        adam.fusion(True)
+
+
 # ------------------------------------------------------------------------------------------
 # activation code 0 ("none")
 # ------------------------------------------------------------------------------------------
