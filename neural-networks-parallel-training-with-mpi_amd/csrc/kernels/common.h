@@ -174,14 +174,16 @@ struct AdamHp {
   float lr, b1, b2, wd, gs, eps, omb1, omb2;
   float step;    // lr / bc1
   float bc2s;    // sqrt(bc2)
+  float bc1, bc2;   // (LAMB divides the moments themselves)
 };
 __device__ __forceinline__ AdamHp adam_hp(const float* __restrict__ hp) {
 #pragma clang fp contract(off)
   AdamHp h;
   h.lr = hp[ADAM_LR]; h.b1 = hp[ADAM_B1]; h.b2 = hp[ADAM_B2]; h.wd = hp[ADAM_WD];
   h.gs = hp[ADAM_GS]; h.eps = hp[ADAM_EPS]; h.omb1 = hp[ADAM_OMB1]; h.omb2 = hp[ADAM_OMB2];
-  h.step = h.lr / hp[ADAM_BC1];
-  h.bc2s = sqrtf(hp[ADAM_BC2]);
+  h.bc1 = hp[ADAM_BC1]; h.bc2 = hp[ADAM_BC2];
+  h.step = h.lr / h.bc1;
+  h.bc2s = sqrtf(h.bc2);
   return h;
 }
 __device__ __forceinline__ float adam_elem(float p, float g, float& m, float& v, const AdamHp& h,
@@ -193,6 +195,28 @@ __device__ __forceinline__ float adam_elem(float p, float g, float& m, float& v,
   m = fmaf(h.b1, m, h.omb1 * d);
   v = fmaf(h.b2, v, (h.omb2 * d) * d);
   return fmaf(-h.step, m / (sqrtf(v) / h.bc2s + h.eps), p);
+}
+
+// LAMB (You et al. 2020, Algorithm 2, identity scaling): the update direction of one element,
+//   u = (m / bc1) / (sqrt(v / bc2) + eps) + wd * p,
+// from the moments of this step.  advance: first move m and v on by the gradient (pass 1);
+// pass 2 calls it with advance = false on the stored moments and the still-unchanged weight and
+// gets the same u bit for bit, so no direction buffer exists.  Contraction pinned as above.
+__device__ __forceinline__ float lamb_dir(float p, float g, float& m, float& v, const AdamHp& h,
+                                          bool advance) {
+#pragma clang fp contract(off)
+  if (advance) {
+    const float d = g * h.gs;
+    m = fmaf(h.b1, m, h.omb1 * d);
+    v = fmaf(h.b2, v, (h.omb2 * d) * d);
+  }
+  const float u = (m / h.bc1) / (sqrtf(v / h.bc2) + h.eps);
+  return h.wd != 0.f ? fmaf(h.wd, p, u) : u;
+}
+// p - lr * r * u with the tensor's trust ratio r
+__device__ __forceinline__ float lamb_step(float p, float u, float lr, float r) {
+#pragma clang fp contract(off)
+  return fmaf(-(lr * r), u, p);
 }
 
 // Element offset of (row n, column k) of a [N][K] bf16 matrix (K % 32 == 0) in its FRAGMENT-MAJOR

@@ -441,6 +441,40 @@ hipError_t sumsq_reduce(const double* part, int nparts, double* out, hipStream_t
 // (norm + 1e-6)) keeping NaN; hp[4] = base_gs * coef; clip_state[2], [3] = norm, coef
 hipError_t clip_finalize(float* hp, float* clip_state, const double* part, int nparts,
                          hipStream_t s);
+// ---- LAMB (optim.hip: the layout comment at its top) ----
+constexpr int LAMB_MAX_TENSORS = 128;   // tensors a block stages in LDS
+constexpr int LAMB_TAB_COLS = 3;        // table row of a tensor: offset, length, first chunk
+constexpr int LAMB_MAX_BLOCKS = 2048;   // grid of the two passes: min(chunks, this)
+// The chunk list of a layout: tensor t (lens[t] elements, any length >= 0) owns
+// ceil(lens[t] / chunk) chunks counted from its start; first[t] (T entries, may be null) = its
+// first chunk.  *nchunks = their number, *part_bytes = the partial buffer pass 1 writes (two
+// doubles per chunk).  chunk: 2048, 4096 or 8192.
+hipError_t lamb_layout(const long long* lens, int T, int chunk, long long* first,
+                       long long* nchunks, long long* part_bytes);
+// Pass 1 over arena elements [off, off + n) (both % 64 == 0; the pointers are the arena's
+// bases): m, v advance, part[2c], part[2c + 1] = the sums of p^2 and u^2 over chunk c's elements
+// inside the range (0 where it has none).  tab: T rows of LAMB_TAB_COLS int64 in device memory.
+hipError_t lamb_moments(const float* p, const float* g, float* m, float* v, const long long* tab,
+                        int T, long long nchunks, int chunk, long long off, long long n,
+                        const float* hp, double* part, hipStream_t s);
+hipError_t lamb_moments_bf16grad(const float* p, const bf16* g, float* m, float* v,
+                                 const long long* tab, int T, long long nchunks, int chunk,
+                                 long long off, long long n, const float* hp, double* part,
+                                 hipStream_t s);
+// One block per tensor: its sums = the chunk partials added in a fixed order, or (gathered:
+// sets x T x 2 doubles, ZeRO-1's per-rank sums) those sets added in set order.  sums_out (may be
+// null): the T x 2 sums; trust / norms (both null: sums only): trust[t] = ||p|| / ||u|| where
+// both are non-zero, else 1 (a NaN stays), norms[2t], [2t + 1] = ||p||, ||u||.
+hipError_t lamb_trust(const double* part, const long long* tab, int T, long long nchunks,
+                      const double* gathered, int sets, double* sums_out, float* trust,
+                      float* norms, hipStream_t s);
+// Pass 2, the chunk mapping of pass 1: p -= lr * trust[tensor] * u over the range, the bf16
+// shadow (may be null), g zeroed (may be null: left alone), the row-band images of `pack`
+// (start[] counted from the arena's base).
+hipError_t lamb_apply(float* p, float* g, const float* m, const float* v, bf16* shadow,
+                      const long long* tab, int T, long long nchunks, int chunk, long long off,
+                      long long n, const float* hp, const float* trust, hipStream_t s,
+                      const SgdPack* pack = nullptr);
 hipError_t cast_f32_bf16(const float* x, bf16* y, long long n, hipStream_t s);
 hipError_t scale_f32(float* x, long long n, float a, hipStream_t s);
 hipError_t cast_bf16_f32(const bf16* x, float* y, long long n, hipStream_t s);

@@ -32,6 +32,29 @@
 //                      it wherever it writes slot 4)
 //    2 last_norm     3 last_coef        -- written by clip_finalize: the pre-clip norm of the
 //                                          scaled gradient and min(1, max_norm / (norm + 1e-6))
+//
+// LAMB (layer-wise trust ratios) is the first pass that knows what a tensor is.  It uses Adam's
+// hyper-parameter tensor and adam_tick, and per arena tensor (padding excluded)
+//
+//    m, v as Adam's;  u = (m / bc1) / (sqrt(v / bc2) + eps) + wd * p;
+//    r = ||p|| / ||u|| where both norms are non-zero, else 1;  p -= lr * r * u
+//
+// in three launches: lamb_moments (m, v and per-chunk sums of p^2 and u^2), lamb_trust (one
+// block per tensor: r), lamb_apply (p, shadow, zeroed gradient, row-band images; u recomputed
+// from the new m, v and the old p, so 24 + 22 bytes move per element and no buffer holds u).
+// Device state, all allocated once per optimizer so captured graphs keep the addresses:
+//
+//    table   int64 [T][3]     offset, length, first chunk of tensor t (lamb_layout)
+//    part    double [chunks][2]   sum p^2, sum u^2 of a chunk's elements inside the pass's range
+//    trust   fp32 [T]         r        norms  fp32 [T][2]   ||p||, ||u|| (reporting)
+//    sums    double [P][T][2] ZeRO-1: every rank's per-tensor sums, all-gathered bitwise
+//
+// A chunk is a compile-time number of elements (4,096; 2,048 and 8,192 are kept for re-measuring,
+// docs/PERF.md §6) counted from its tensor's 64-aligned start -- the last one ragged, never
+// across two tensors; blocks take whole chunks block-stride,
+// so which additions form which partial depends on the arena layout alone: all of fixed order
+// (a thread's elements in index order, the LDS tree, the chunks of a tensor in index order) and
+// none atomic -- same bits on every run and rank.
 #include "common.h"
 #include "kernels.h"
 #include "knobs.h"
@@ -390,6 +413,304 @@ hipError_t adam_update_bf16grad(float* p, const bf16* g, float* m, float* v, bf1
 hipError_t adam_tick(float* hp, int* t, hipStream_t s) {
   if (!hp || !t) return hipErrorInvalidValue;
   hipLaunchKernelGGL(adam_tick_kernel, dim3(1), dim3(1), 0, s, hp, t);
+  return hipGetLastError();
+}
+
+// ---- LAMB ----
+// The tensor table as a block holds it in LDS, and chunk c resolved against it: its tensor, its
+// first element cs and the part [lo, hi) of it inside the pass's range [r0, r1).  cs, r0 and r1
+// are multiples of 64, so a float4 is never cut at lo; hi cuts one only at a tensor's ragged end.
+struct LambTab {
+  long long off[LAMB_MAX_TENSORS], len[LAMB_MAX_TENSORS];
+  long long first[LAMB_MAX_TENSORS];
+};
+struct LambChunk {
+  int t;
+  long long cs, lo, hi;
+};
+
+__device__ __forceinline__ void lamb_stage(LambTab& s, const long long* __restrict__ tab, int T) {
+  for (int t = threadIdx.x; t < T; t += 256) {
+    s.off[t] = tab[LAMB_TAB_COLS * t];
+    s.len[t] = tab[LAMB_TAB_COLS * t + 1];
+    s.first[t] = tab[LAMB_TAB_COLS * t + 2];
+  }
+  __syncthreads();
+}
+
+template <int CH>
+__device__ __forceinline__ LambChunk lamb_chunk(const LambTab& s, int T, long long c, long long r0,
+                                                long long r1) {
+  int a = 0, b = T - 1;   // the last tensor whose first chunk is <= c (an empty tensor owns none)
+  while (a < b) {
+    const int mid = (a + b + 1) >> 1;
+    if (s.first[mid] <= c) a = mid; else b = mid - 1;
+  }
+  LambChunk k;
+  k.t = a;
+  k.cs = s.off[a] + (c - s.first[a]) * CH;
+  const long long te = s.off[a] + s.len[a], ce = k.cs + CH < te ? k.cs + CH : te;
+  k.lo = k.cs > r0 ? k.cs : r0;
+  k.hi = ce < r1 ? ce : r1;
+  return k;
+}
+
+// elements of the float4 at e that lie inside [lo, hi): 0 (not this pass's), 4, or 1..3 at a
+// tensor's ragged end (the float4 is still loaded whole: every tensor is padded to 64 elements)
+__device__ __forceinline__ int lamb_count(long long e, long long lo, long long hi) {
+  if (e < lo || e >= hi) return 0;
+  return hi - e >= 4 ? 4 : (int)(hi - e);
+}
+
+// Pass 1.  A block takes whole chunks, block-stride; thread t owns the float4s t, t + 256, ... of
+// a chunk (all loads of the chunk in flight before the first use).  m and v advance, u is formed
+// and dropped; the chunk's two sums go thread (element order) -> LDS tree -> part[c].
+template <typename TG, int CH>
+__global__ void __launch_bounds__(256) lamb_moments_kernel(
+    const float* __restrict__ p, TG* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
+    const long long* __restrict__ tab, int T, long long nchunks, long long r0, long long r1,
+    const float* __restrict__ hp, double* __restrict__ part) {
+  constexpr int NI = CH / 1024;
+  __shared__ LambTab s;
+  __shared__ double red[2][256];
+  lamb_stage(s, tab, T);
+  const AdamHp h = adam_hp(hp);
+  const int tid = threadIdx.x;
+  for (long long c = blockIdx.x; c < nchunks; c += gridDim.x) {
+    const LambChunk k = lamb_chunk<CH>(s, T, c, r0, r1);
+    if (k.lo >= k.hi) {   // (block-uniform) nothing of this chunk lies in the range
+      if (tid == 0) { part[2 * c] = 0.0; part[2 * c + 1] = 0.0; }
+      continue;
+    }
+    f32x4 pv[NI], gv[NI], mv[NI], vv[NI];
+    int cnt[NI];
+#pragma unroll
+    for (int i = 0; i < NI; ++i) {
+      const long long e = k.cs + 4LL * (tid + 256 * i);
+      cnt[i] = lamb_count(e, k.lo, k.hi);
+      if (cnt[i]) {
+        pv[i] = reinterpret_cast<const f32x4*>(p)[e / 4];
+        gv[i] = load_grad4(g, e / 4);
+        mv[i] = reinterpret_cast<const f32x4*>(m)[e / 4];
+        vv[i] = reinterpret_cast<const f32x4*>(v)[e / 4];
+      }
+    }
+    double sp = 0.0, su = 0.0;
+#pragma unroll
+    for (int i = 0; i < NI; ++i) {
+      if (!cnt[i]) continue;
+      const long long e = k.cs + 4LL * (tid + 256 * i);
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        float mm = mv[i][r], ss = vv[i][r];
+        const float u = lamb_dir(pv[i][r], gv[i][r], mm, ss, h, true);
+        mv[i][r] = mm;
+        vv[i][r] = ss;
+        if (r < cnt[i]) {   // (each fp32 square is exact in double)
+          sp += (double)pv[i][r] * (double)pv[i][r];
+          su += (double)u * (double)u;
+        }
+      }
+      if (cnt[i] == 4) {
+        reinterpret_cast<f32x4*>(m)[e / 4] = mv[i];
+        reinterpret_cast<f32x4*>(v)[e / 4] = vv[i];
+      } else {
+        for (int r = 0; r < cnt[i]; ++r) { m[e + r] = mv[i][r]; v[e + r] = vv[i][r]; }
+      }
+    }
+    red[0][tid] = sp;
+    red[1][tid] = su;
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {
+      if (tid < o) { red[0][tid] += red[0][tid + o]; red[1][tid] += red[1][tid + o]; }
+      __syncthreads();
+    }
+    if (tid == 0) { part[2 * c] = red[0][0]; part[2 * c + 1] = red[1][0]; }
+  }
+}
+
+// One block per tensor.  Its two sums: the tensor's chunk partials (thread t adds chunks t,
+// t + 256, ... in that order, then the LDS tree), or -- gathered -- the `sets` per-rank sums in
+// rank order.  Then the ratio, in double, rounded once.
+__global__ void __launch_bounds__(256) lamb_trust_kernel(
+    const double* __restrict__ part, const long long* __restrict__ tab, int T, long long nchunks,
+    const double* __restrict__ gathered, int sets, double* __restrict__ sums_out,
+    float* __restrict__ trust, float* __restrict__ norms) {
+  __shared__ double red[2][256];
+  const int t = blockIdx.x, tid = threadIdx.x;
+  double sp = 0.0, su = 0.0;
+  if (gathered) {
+    if (tid == 0)
+      for (int q = 0; q < sets; ++q) {
+        sp += gathered[((long long)q * T + t) * 2];
+        su += gathered[((long long)q * T + t) * 2 + 1];
+      }
+  } else {
+    const long long c0 = tab[LAMB_TAB_COLS * t + 2];
+    const long long c1 = t + 1 < T ? tab[LAMB_TAB_COLS * (t + 1) + 2] : nchunks;
+    for (long long c = c0 + tid; c < c1; c += 256) { sp += part[2 * c]; su += part[2 * c + 1]; }
+    red[0][tid] = sp;
+    red[1][tid] = su;
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {
+      if (tid < o) { red[0][tid] += red[0][tid + o]; red[1][tid] += red[1][tid + o]; }
+      __syncthreads();
+    }
+    sp = red[0][0];
+    su = red[1][0];
+  }
+  if (tid != 0) return;
+  if (sums_out) { sums_out[2 * t] = sp; sums_out[2 * t + 1] = su; }
+  if (!trust) return;
+  const double pn = sqrt(sp), un = sqrt(su);
+  // both norms non-zero: their ratio (a NaN norm gives a NaN); else 1
+  const double r = (pn == 0.0 || un == 0.0) ? 1.0 : pn / un;
+  trust[t] = (float)r;
+  norms[2 * t] = (float)pn;
+  norms[2 * t + 1] = (float)un;
+}
+
+// Pass 2, the chunk mapping of pass 1: u again from the stored m, v and the unchanged p (the same
+// lamb_dir, so the same bits), then the step with the tensor's ratio.
+template <int CH>
+__global__ void __launch_bounds__(256) lamb_apply_kernel(
+    float* __restrict__ p, float* __restrict__ g, const float* __restrict__ m,
+    const float* __restrict__ v, bf16* __restrict__ shadow, const long long* __restrict__ tab, int T,
+    long long nchunks, long long r0, long long r1, const float* __restrict__ hp,
+    const float* __restrict__ trust, SgdPack pk) {
+  constexpr int NI = CH / 1024;
+  __shared__ LambTab s;
+  lamb_stage(s, tab, T);
+  const AdamHp h = adam_hp(hp);
+  const int tid = threadIdx.x;
+  for (long long c = blockIdx.x; c < nchunks; c += gridDim.x) {
+    const LambChunk k = lamb_chunk<CH>(s, T, c, r0, r1);
+    if (k.lo >= k.hi) continue;
+    const float ratio = trust[k.t];
+    f32x4 pv[NI], mv[NI], vv[NI];
+    int cnt[NI];
+#pragma unroll
+    for (int i = 0; i < NI; ++i) {
+      const long long e = k.cs + 4LL * (tid + 256 * i);
+      cnt[i] = lamb_count(e, k.lo, k.hi);
+      if (cnt[i]) {
+        pv[i] = reinterpret_cast<const f32x4*>(p)[e / 4];
+        mv[i] = reinterpret_cast<const f32x4*>(m)[e / 4];
+        vv[i] = reinterpret_cast<const f32x4*>(v)[e / 4];
+      }
+    }
+#pragma unroll
+    for (int i = 0; i < NI; ++i) {
+      if (!cnt[i]) continue;
+      const long long e = k.cs + 4LL * (tid + 256 * i);
+      bf16x4 sv;
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        float mm = mv[i][r], ss = vv[i][r];
+        const float u = lamb_dir(pv[i][r], 0.f, mm, ss, h, false);
+        pv[i][r] = lamb_step(pv[i][r], u, h.lr, ratio);
+        sv[r] = (bf16)pv[i][r];
+      }
+      if (cnt[i] < 4) {   // a tensor's ragged end: its elements only, the padding keeps its bytes
+        for (int r = 0; r < cnt[i]; ++r) {
+          p[e + r] = pv[i][r];
+          if (shadow) shadow[e + r] = sv[r];
+          if (g) g[e + r] = 0.f;
+        }
+        continue;
+      }
+      reinterpret_cast<f32x4*>(p)[e / 4] = pv[i];
+      if (shadow) reinterpret_cast<bf16x4*>(shadow)[e / 4] = sv;
+      if (g) reinterpret_cast<f32x4*>(g)[e / 4] = f32x4{0.f, 0.f, 0.f, 0.f};
+      for (int q = 0; q < pk.n; ++q) {   // row-band v2 weight images of the updated weights
+        const long long loc = e - pk.start[q];
+        if (loc >= 0 && loc < (long long)pk.M[q] * pk.N[q]) {
+          const int row = (int)(loc / pk.N[q]), col = (int)(loc % pk.N[q]);
+          rb_pack_store4(pk.pkf[q], pk.pkd[q], row, col, pk.M[q], pk.N[q], pv[i]);
+        }
+      }
+    }
+  }
+}
+
+hipError_t lamb_layout(const long long* lens, int T, int chunk, long long* first,
+                       long long* nchunks, long long* part_bytes) {
+  if (!lens || !nchunks || !part_bytes || T < 1 || T > LAMB_MAX_TENSORS ||
+      (chunk != 2048 && chunk != 4096 && chunk != 8192))
+    return hipErrorInvalidValue;
+  long long c = 0;
+  for (int t = 0; t < T; ++t) {
+    if (lens[t] < 0) return hipErrorInvalidValue;
+    if (first) first[t] = c;
+    c += (lens[t] + chunk - 1) / chunk;
+  }
+  *nchunks = c;
+  *part_bytes = c * 2 * (long long)sizeof(double);
+  return hipSuccess;
+}
+
+static bool lamb_range_ok(const void* tab, int T, long long nchunks, int chunk, long long off,
+                          long long n) {
+  return tab && T >= 1 && T <= LAMB_MAX_TENSORS && nchunks >= 0 && off >= 0 && n >= 0 &&
+         off % 64 == 0 && n % 64 == 0 && (chunk == 2048 || chunk == 4096 || chunk == 8192);
+}
+
+static int lamb_grid(long long nchunks) {
+  return (int)std::min<long long>(nchunks, LAMB_MAX_BLOCKS);
+}
+
+template <typename TG>
+static hipError_t lamb_moments_launch(const float* p, TG* g, float* m, float* v,
+                                      const long long* tab, int T, long long nchunks, int chunk,
+                                      long long off, long long n, const float* hp, double* part,
+                                      hipStream_t s) {
+  if (!p || !g || !m || !v || !hp || !part || !lamb_range_ok(tab, T, nchunks, chunk, off, n))
+    return hipErrorInvalidValue;
+  if (nchunks == 0) return hipSuccess;
+  auto* f = chunk == 2048 ? lamb_moments_kernel<TG, 2048>
+          : chunk == 4096 ? lamb_moments_kernel<TG, 4096> : lamb_moments_kernel<TG, 8192>;
+  hipLaunchKernelGGL(f, dim3(lamb_grid(nchunks)), dim3(256), 0, s, p, g, m, v, tab, T, nchunks,
+                     off, off + n, hp, part);
+  return hipGetLastError();
+}
+
+hipError_t lamb_moments(const float* p, const float* g, float* m, float* v, const long long* tab,
+                        int T, long long nchunks, int chunk, long long off, long long n,
+                        const float* hp, double* part, hipStream_t s) {
+  return lamb_moments_launch<const float>(p, g, m, v, tab, T, nchunks, chunk, off, n, hp, part, s);
+}
+
+hipError_t lamb_moments_bf16grad(const float* p, const bf16* g, float* m, float* v,
+                                 const long long* tab, int T, long long nchunks, int chunk,
+                                 long long off, long long n, const float* hp, double* part,
+                                 hipStream_t s) {
+  return lamb_moments_launch<const bf16>(p, g, m, v, tab, T, nchunks, chunk, off, n, hp, part, s);
+}
+
+hipError_t lamb_trust(const double* part, const long long* tab, int T, long long nchunks,
+                      const double* gathered, int sets, double* sums_out, float* trust,
+                      float* norms, hipStream_t s) {
+  if (!tab || T < 1 || T > LAMB_MAX_TENSORS || nchunks < 0 || (!gathered && !part) ||
+      (gathered && sets < 1) || (!trust != !norms) || (!trust && !sums_out))
+    return hipErrorInvalidValue;
+  hipLaunchKernelGGL(lamb_trust_kernel, dim3(T), dim3(256), 0, s, part, tab, T, nchunks, gathered,
+                     sets, sums_out, trust, norms);
+  return hipGetLastError();
+}
+
+hipError_t lamb_apply(float* p, float* g, const float* m, const float* v, bf16* shadow,
+                      const long long* tab, int T, long long nchunks, int chunk, long long off,
+                      long long n, const float* hp, const float* trust, hipStream_t s,
+                      const SgdPack* pack) {
+  if (!p || !m || !v || !hp || !trust || !pack_ok(pack) ||
+      !lamb_range_ok(tab, T, nchunks, chunk, off, n))
+    return hipErrorInvalidValue;
+  if (nchunks == 0 || n == 0) return hipSuccess;
+  const SgdPack pk = pack ? *pack : SgdPack{};
+  auto* f = chunk == 2048 ? lamb_apply_kernel<2048>
+          : chunk == 4096 ? lamb_apply_kernel<4096> : lamb_apply_kernel<8192>;
+  hipLaunchKernelGGL(f, dim3(lamb_grid(nchunks)), dim3(256), 0, s, p, g, m, v, shadow, tab, T,
+                     nchunks, off, off + n, hp, trust, pk);
   return hipGetLastError();
 }
 

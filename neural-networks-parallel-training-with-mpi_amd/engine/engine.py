@@ -90,8 +90,8 @@ class MLPEngine:
                  rowband_plan: Optional[int] = None, optimizer: str = "sgd", beta1: float = 0.9,
                  beta2: float = 0.999, eps: float = 1e-8,
                  clip_grad_norm: Optional[float] = None):
-        """``optimizer``: ``sgd`` (momentum / dampening / nesterov apply), ``adam`` or ``adamw``
-        (beta1 / beta2 / eps apply; ``momentum`` is ignored).  ``weight_decay`` is shared.
+        """``optimizer``: ``sgd`` (momentum / dampening / nesterov apply), ``adam``, ``adamw`` or
+        ``lamb`` (beta1 / beta2 / eps apply; ``momentum`` is ignored).  ``weight_decay`` is shared.
         ``clip_grad_norm``: clip the (reduced, averaged) gradient to this global L2 norm before
         every update, as ``torch.nn.utils.clip_grad_norm_`` does -- norm and coefficient are
         computed on the device inside the step (engine/optimizer.py); None: off."""
@@ -1122,6 +1122,14 @@ class MLPEngine:
     def clip_coef(self) -> float:
         """The last step's clip coefficient min(1, max_norm / (norm + 1e-6)) (host sync)."""
         return self._clip_slot(3)
+
+    def trust_ratios(self) -> dict:
+        """LAMB: ``{slot name: (trust ratio, |p|, |u|)}`` of the last step's update, one entry
+        per arena tensor (host sync).  Raises under another optimizer: nothing computes them."""
+        if self.opt.name != "lamb":
+            raise RuntimeError(f"trust ratios exist under --optimizer lamb, not {self.opt.name}")
+        self.synchronize()
+        return self.opt.trust_ratios()
 
     def synchronize(self, check: bool = True):
         """Wait for the engine's stream.  ``check``: then raise if a column-split row-band step

@@ -14,6 +14,8 @@ combines, the tiny step, the deferred epilogue) gets its operand tuple from :met
   takes the unfused form of every schedule under it.  Its step number lives on the device:
   :meth:`tick`, the first launch of every optimizer step, advances it and refreshes the bias
   corrections in the hyper-parameter tensor, so a replayed graph of N steps counts N steps.
+* :class:`Lamb` -- ``ops.lamb``: Adam's moments with a trust ratio per arena tensor.  Built on
+  :class:`Adam`; like a clipped step it needs the whole reduced gradient (:attr:`whole_grad`).
 
 Hyper-parameter tensor: slots 0 / 3 / 4 (lr, weight decay, gradient scale) mean the same under
 both, so ``MLPEngine.set_hparams`` / ``set_scales`` do not care which one is active.  The Adam
@@ -32,7 +34,7 @@ import torch
 SGD_HP_LEN = 8
 ADAM_HP_LEN = 12
 CLIP_MAX_PARTS = 1024     # float64 partials of grad_sumsq (kernels.h)
-OPTIMIZERS = ("sgd", "adam", "adamw")
+OPTIMIZERS = ("sgd", "adam", "adamw", "lamb")
 
 
 def _f32(x: float) -> float:
@@ -85,6 +87,12 @@ class _Clipped:
     def clipping(self) -> bool:
         return self.clip_state is not None
 
+    @property
+    def whole_grad(self) -> bool:
+        """No update may be issued before the whole reduced gradient exists (the bucket pipeline
+        then holds every bucket's update until its join): a clipped step -- and LAMB, always."""
+        return self.clipping
+
     def clip(self, offset: int = 0, numel: Optional[int] = None, grad_bf16=None, gather=None):
         """Norm of ``[offset, offset + numel)`` of the reduced gradient (``grad_bf16``: of the
         bf16 payload the update will read) and the finalize, on the current stream.
@@ -116,7 +124,8 @@ class Sgd(_Clipped):
         self._init_clip(clip_grad_norm)
 
     def apply(self, first: bool, offset: int = 0, numel: Optional[int] = None,
-              zero_grad: bool = True, grad_bf16=None, images=None):
+              zero_grad: bool = True, grad_bf16=None, images=None, gather=None):
+        # (``gather``: ZeRO-1's all-gather of per-rank sums, see Lamb.apply; not needed here)
         self.ops.sgd(self.arena, self.hp, self.nesterov, first, zero_grad=zero_grad,
                      offset=offset, numel=numel, grad_bf16=grad_bf16, images=images)
 
@@ -149,8 +158,9 @@ class Adam(_Clipped):
         self._init_clip(clip_grad_norm)
 
     def apply(self, first: bool, offset: int = 0, numel: Optional[int] = None,
-              zero_grad: bool = True, grad_bf16=None, images=None):
-        # (``first`` is SGD's momentum initialisation; Adam starts from zero state)
+              zero_grad: bool = True, grad_bf16=None, images=None, gather=None):
+        # (``first`` is SGD's momentum initialisation; Adam starts from zero state; ``gather``
+        # is for Lamb.apply)
         self.ops.adam(self.arena, self.hp, self.t, self.decoupled, zero_grad=zero_grad,
                       offset=offset, numel=numel, grad_bf16=grad_bf16, images=images)
 
@@ -169,9 +179,42 @@ class Adam(_Clipped):
         return [self.arena.momentum, self.arena.exp_avg_sq]
 
 
+class Lamb(Adam):
+    """Layer-wise adaptive moments (You et al. 2020, Algorithm 2, identity scaling): Adam's
+    moments, hyper-parameter tensor, tick and state buffers; per arena tensor -- every weight and
+    every bias, padding excluded -- the step is scaled by the trust ratio ``|p| / |u|`` of the
+    weight's norm to the norm of the update direction ``u`` (``--weight_decay`` is the decay
+    inside ``u``).  The ratios need the whole reduced gradient, so no update is issued before it
+    exists (:attr:`whole_grad`): every site applies one whole-range update.  ``state`` (the chunk
+    table, the partial sums, the ratios and norms: ops/base.py LambState) is allocated here,
+    once.  Slot 4 scales the gradient as under Adam, so clipping composes unchanged."""
+    name = "lamb"
+    whole_grad = True
+
+    def __init__(self, ops, arena, hp, clip_grad_norm=None):
+        super().__init__(ops, arena, hp, decoupled=False, clip_grad_norm=clip_grad_norm)
+        self.name = "lamb"
+        self.state = ops.lamb_state(arena)
+
+    def apply(self, first: bool, offset: int = 0, numel: Optional[int] = None,
+              zero_grad: bool = True, grad_bf16=None, images=None, gather=None):
+        """``gather = (world, rank, allgather)``: the range is this rank's ZeRO-1 slice; the
+        per-tensor sums of all ranks are all-gathered and added in rank order (ops ``lamb``)."""
+        self.ops.lamb(self.arena, self.hp, self.t, zero_grad=zero_grad, offset=offset,
+                      numel=numel, grad_bf16=grad_bf16, images=images, gather=gather,
+                      state=self.state)
+
+    def trust_ratios(self):
+        """{tensor name: (ratio, |p|, |u|)} of the last update (copies to the host)."""
+        r, nm = self.state.trust.tolist(), self.state.norms.tolist()
+        return {k: (r[i], nm[2 * i], nm[2 * i + 1]) for i, k in enumerate(self.state.names)}
+
+
 def make_optimizer(name: str, ops, arena, hp, nesterov: bool = False,
                    clip_grad_norm: Optional[float] = None):
     """``clip_grad_norm``: clip the gradient to this global L2 norm (None: off)."""
+    if name == "lamb":
+        return Lamb(ops, arena, hp, clip_grad_norm)
     if name == "sgd":
         return Sgd(ops, arena, hp, nesterov, clip_grad_norm)
     if name in ("adam", "adamw"):

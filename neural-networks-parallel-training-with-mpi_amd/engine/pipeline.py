@@ -71,7 +71,7 @@ class BucketPipeline:
         self.sgd_done = set()                 # buckets whose update is queued or issued
         self.reduced = {}                     # bucket index -> stream its collective completes on
         self.pending: List[Tuple[object, object]] = []   # (bucket, stream) updates not issued yet
-        self.held: List[object] = []          # clipping: reduced buckets, updated behind the join
+        self.held: List[object] = []          # clipping / LAMB: reduced buckets, updated behind the join
         self.written16: List[Tuple[int, int]] = []       # arena ranges stored as bf16 payload
         self.waited = set()                   # partner layers the compute stream has waited for
         # keywords of every bucket update: the bf16 payload, the row-band images to refresh
@@ -123,9 +123,9 @@ class BucketPipeline:
             rs = self.bucket_reduce(b, stream)
             if rs is None or rs is stream:
                 continue   # reduced on this stream already (single rank): update once at the end
-            if self.opt.clipping:
-                # the clip coefficient needs the whole reduced gradient: the collectives still
-                # overlap the backward, every update waits for join()
+            if self.opt.whole_grad:
+                # the clip coefficient (LAMB: the trust ratios) needs the whole reduced gradient:
+                # the collectives still overlap the backward, every update waits for join()
                 self.held.append(b)
                 continue
             self.pending.append((b, rs))
@@ -192,8 +192,8 @@ class BucketPipeline:
         tail, self.pending = self.pending, []
         self.sync.finish()   # joins the comm stream into the compute stream
         if self.held:
-            # clipping, per-bucket collectives: one norm of the whole reduced gradient (of the
-            # bf16 payload when that is what the update reads), one finalize, one update
+            # clipping / LAMB, per-bucket collectives: one norm of the whole reduced gradient (of
+            # the bf16 payload when that is what the update reads), one finalize, one update
             self.held = []
             if joined is not None:
                 joined()

@@ -9,7 +9,8 @@ Per rank:
      (ref.py:87-88) into the flat arena that backs the model's parameters;
   4. run the epoch loop: one optimizer step per batch (full shard by default, ref.py:146),
      gradients synchronised by bucketed all-reduce, fused SGD-momentum (or ``--optimizer adam``
-     / ``adamw``: one Adam pass of the same shape); print the reference's
+     / ``adamw``: one Adam pass of the same shape; ``lamb``: two passes around the per-tensor
+     trust ratios); print the reference's
      two log lines (ref.py:152,224);
   5. optionally checkpoint (reference-format state_dict) / resume, emit JSON metrics.
 """
@@ -638,6 +639,9 @@ def _run(j: Job) -> TrainResult:
         if clipping:
             res.schedule.update(clip_grad_norm=float(cfg.clip_grad_norm),
                                 grad_norms=list(res.grad_norms), clip_coefs=list(res.clip_coefs))
+        if eng.opt.name == "lamb":
+            # per tensor, the last step's [trust ratio, |p|, |u|] (travels with the rank results)
+            res.schedule["trust_ratios"] = {k: list(v) for k, v in eng.trust_ratios().items()}
         if eng.timer is not None:
             res.phase_ms = eng.timer.summary_ms()
             _print(cfg, rank, "[profile] mean ms per step: " +

@@ -16,6 +16,34 @@ def yes(*args, **kw) -> bool:
     return True
 
 
+class LambState:
+    """What a LAMB optimizer keeps on the device besides exp_avg / exp_avg_sq (layout: the top of
+    csrc/kernels/optim.hip).  One tensor per ``Arena.slots`` entry, in arena order."""
+
+    def __init__(self, ops, arena):
+        import torch
+        self.names = [s.name for s in arena.slots]
+        self.ranges = [(s.offset, s.numel) for s in arena.slots]
+        self.T, self.chunk = len(self.ranges), int(ops.lamb_chunk)
+        first, self.nchunks = ops.lamb_layout([n for _, n in self.ranges], self.chunk)
+        dev = arena.master.device
+        self.table = torch.tensor([[o, n, f] for (o, n), f in zip(self.ranges, first)],
+                                  dtype=torch.int64, device=dev).reshape(-1)
+        self.part = torch.zeros(2 * max(1, self.nchunks), dtype=torch.float64, device=dev)
+        self.trust = torch.ones(self.T, dtype=torch.float32, device=dev)
+        self.norms = torch.zeros(2 * self.T, dtype=torch.float32, device=dev)
+        self._sums = None
+
+    def sums(self, sets: int = 1):
+        """float64 [sets][T][2]: per-tensor (sum p^2, sum u^2) of ``sets`` ranks or ranges
+        (allocated on first use -- a first step runs eagerly, ahead of any capture)."""
+        if self._sums is None or self._sums.shape[0] != sets:
+            import torch
+            self._sums = torch.zeros(sets, self.T, 2, dtype=torch.float64,
+                                     device=self.table.device)
+        return self._sums
+
+
 class OpSet:
     # the op set has tiny_step / sgd_fusion / the weight gradients that store the bf16
     # all-reduce payload themselves (linear_wgrad(out_bf16=), linear_wgrad_defer)
@@ -40,6 +68,34 @@ class OpSet:
         """From the summed partials: ``hp[4]`` = base scale x clip coefficient, and the norm and
         the coefficient into ``clip_state`` ([max_norm, base_gs, last_norm, last_coef])."""
         raise NotImplementedError(f"{type(self).__name__}: clip_finalize is not supported")
+
+    # ---- LAMB (csrc/kernels/optim.hip; TorchOps is the CPU training path) ----
+    lamb_chunk = 4096       # elements per chunk of the per-tensor reduction (HipOps: measured)
+
+    def lamb_layout(self, lens, chunk: int):
+        """(first chunk of every tensor, number of chunks) of tensors of ``lens`` elements."""
+        first, c = [], 0
+        for n in lens:
+            first.append(c)
+            c += (n + chunk - 1) // chunk
+        return first, c
+
+    def lamb_state(self, arena) -> "LambState":
+        """The device state of a LAMB optimizer over ``arena``, allocated once (captured graphs
+        keep its addresses)."""
+        return LambState(self, arena)
+
+    def lamb(self, arena, hp, t, zero_grad: bool = True, offset: int = 0, numel=None,
+             grad_bf16=None, images=None, gather=None, state=None):
+        """LAMB over ``[offset, offset + numel)`` (multiples of 64), the keywords of ``adam``.
+        Per arena tensor: ``u = (m / bc1) / (sqrt(v / bc2) + eps) + wd * p``, ``r = |p| / |u|``
+        where both norms are non-zero (else 1), ``p -= lr * r * u``; the norms cover the
+        tensor's elements inside the range.  ``gather = (world, rank, allgather)`` (ZeRO-1: the
+        range is this rank's slice): ``allgather(buf)`` gathers the ``world`` equal parts of the
+        float64 ``buf`` in place, bitwise (part ``rank`` is this rank's); the per-rank sums are
+        then added in rank order, so every rank holds the same ratios.  ``state``: the
+        optimizer's :class:`LambState` (default: one kept with the arena)."""
+        raise NotImplementedError(f"{type(self).__name__}: lamb is not supported")
 
     # ---- forward-only output layer (csrc/kernels/head_eval.hip; TorchOps is the oracle) ----
     def head_eval(self, a, W, b, y=None, labels=None, loss=None, logits_out=None, pred_out=None,

@@ -572,6 +572,97 @@ class HipOps(OpSet):
         self.lib.adam_update(_p(arena.master) + e * offset, _p(arena.grad) + e * offset, *args,
                              int(zero_grad), self.stream, pack)
 
+    # ---- LAMB: lamb_moments -> lamb_trust -> lamb_apply (optim.hip) ----
+    @property
+    def lamb_chunk(self) -> int:
+        """Elements per chunk: 4,096 measured best of 2,048 / 4,096 / 8,192 (docs/PERF.md §6)."""
+        return int(knob("NNMPI_LAMB_CHUNK", "4096"))
+
+    def lamb_layout(self, lens, chunk: int):
+        first, nchunks, _ = self.lib.lamb_layout([int(n) for n in lens], int(chunk))
+        return list(first), int(nchunks)
+
+    def _lamb_range(self, arena, st, offset: int, numel, what: str) -> int:
+        """The checks every LAMB launch shares (the kernels trust the state's table and sizes):
+        returns numel."""
+        n = arena.numel - offset if numel is None else numel
+        _check(arena.exp_avg_sq is not None, f"{what}: the arena has no exp_avg_sq buffer "
+                                             "(Arena.ensure_exp_avg_sq)")
+        _check(n % 64 == 0 and offset % 64 == 0,
+               f"{what}: offset and numel % 64 == 0 ({offset}, {n})")
+        _check(0 <= offset and 0 <= n and offset + n <= arena.numel,
+               f"{what}: range outside the arena")
+        _check(st.T <= int(self.lib.LAMB_MAX_TENSORS) and st.table.numel() == 3 * st.T and
+               st.part.numel() >= 2 * st.nchunks and st.trust.numel() >= st.T and
+               st.norms.numel() >= 2 * st.T and
+               all(o % 64 == 0 and o + k <= arena.numel for o, k in st.ranges),
+               f"{what}: the state does not fit the arena")
+        return n
+
+    def lamb_moments(self, arena, hp, st, offset: int = 0, numel: int = None, grad_bf16=None):
+        """Pass 1: exp_avg / exp_avg_sq advance over the range; ``st.part`` gets every chunk's
+        (sum p^2, sum u^2) over its elements inside the range."""
+        n = self._lamb_range(arena, st, offset, numel, "lamb_moments")
+        _check(hp.dtype == torch.float32 and hp.numel() >= int(self.lib.ADAM_HP_LEN),
+               "lamb: the 12-slot Adam hyper-parameter tensor")
+        args = (_p(arena.momentum), _p(arena.exp_avg_sq), _p(st.table), st.T, st.nchunks, st.chunk,
+                offset, n, _p(hp), _p(st.part), self.stream)
+        if grad_bf16 is not None:
+            _check(grad_bf16.dtype == torch.bfloat16 and grad_bf16.numel() >= offset + n,
+                   "lamb: bf16 gradient buffer too small")
+            self.lib.lamb_moments_bf16grad(_p(arena.master), _p(grad_bf16), *args)
+        else:
+            self.lib.lamb_moments(_p(arena.master), _p(arena.grad), *args)
+
+    def lamb_trust(self, st, gathered=None, sums_out=None, ratios: bool = True):
+        """Per tensor: the chunk partials of ``st.part`` summed (or the sets of ``gathered``,
+        float64 [sets][T][2], added in set order) into ``sums_out`` (float64 [T][2], optional)
+        and, with ``ratios``, into ``st.trust`` / ``st.norms``."""
+        sets = 0
+        if gathered is not None:
+            _check(gathered.dtype == torch.float64 and gathered.is_contiguous() and
+                   gathered.dim() == 3 and tuple(gathered.shape[1:]) == (st.T, 2),
+                   "lamb_trust: gathered sums are float64 [sets][T][2]")
+            sets = gathered.shape[0]
+        if sums_out is not None:
+            _check(sums_out.dtype == torch.float64 and sums_out.is_contiguous() and
+                   sums_out.numel() == 2 * st.T, "lamb_trust: sums_out is float64 [T][2]")
+        _check(ratios or sums_out is not None, "lamb_trust: nothing to write")
+        self.lib.lamb_trust(_p(st.part), _p(st.table), st.T, st.nchunks, _p(gathered), sets,
+                            _p(sums_out), _p(st.trust) if ratios else 0,
+                            _p(st.norms) if ratios else 0, self.stream)
+
+    def lamb_apply(self, arena, hp, st, zero_grad: bool = True, offset: int = 0, numel: int = None,
+                   images=None):
+        """Pass 2: ``p -= lr * st.trust[tensor] * u`` over the range, the bf16 shadow, the zeroed
+        fp32 gradient (``zero_grad``) and the row-band ``images``."""
+        n = self._lamb_range(arena, st, offset, numel, "lamb_apply")
+        self.lib.lamb_apply(_p(arena.master), _p(arena.grad) if zero_grad else 0,
+                            _p(arena.momentum), _p(arena.exp_avg_sq), _p(arena.shadow),
+                            _p(st.table), st.T, st.nchunks, st.chunk, offset, n, _p(hp),
+                            _p(st.trust), self.stream,
+                            self._image_pack(arena, images, 0, arena.numel))
+
+    def lamb(self, arena, hp, t, zero_grad: bool = True, offset: int = 0, numel: int = None,
+             grad_bf16=None, images=None, gather=None, state=None):
+        """See :meth:`OpSet.lamb`.  Three launches (five under ``gather``: the rank's sums, the
+        collective, the ratios); ``t`` is not read, as in :meth:`adam`."""
+        st = state
+        if st is None:
+            st = getattr(arena, "_lamb_state", None)
+            if st is None:
+                st = arena._lamb_state = self.lamb_state(arena)
+        self.lamb_moments(arena, hp, st, offset, numel, grad_bf16)
+        if gather is None:
+            self.lamb_trust(st)
+        else:
+            world, rank, allgather = gather
+            sums = st.sums(world)
+            self.lamb_trust(st, sums_out=sums[rank], ratios=False)
+            allgather(sums)
+            self.lamb_trust(st, gathered=sums)
+        self.lamb_apply(arena, hp, st, zero_grad and grad_bf16 is None, offset, numel, images)
+
     def sgd(self, arena, hp, nesterov: bool, first: bool, zero_grad: bool = True, offset: int = 0,
             numel: int = None, grad_bf16=None, images=None):
         """``grad_bf16``: read the gradient from this bf16 buffer (same layout as the arena)

@@ -216,3 +216,57 @@ class TorchOps(OpSet):
                 arena.shadow[sl].copy_(p)
             if zero_grad:
                 g.zero_()
+
+    def lamb(self, arena, hp, t, zero_grad: bool = True, offset: int = 0, numel: int = None,
+             grad_bf16=None, images=None, gather=None, state=None):
+        """LAMB in plain torch (see :meth:`OpSet.lamb`): the kernels' element formula in fp32,
+        the per-tensor sums of squares in float64, tensor by tensor over the parts inside the
+        range; padding is left alone."""
+        if images:
+            raise ValueError("TorchOps.lamb: the row-band weight images are a HIP path")
+        st = state
+        if st is None:
+            st = getattr(arena, "_lamb_state", None)
+            if st is None:
+                st = arena._lamb_state = self.lamb_state(arena)
+        n = arena.numel - offset if numel is None else numel
+        if offset % 64 or n % 64 or offset < 0 or n < 0 or offset + n > arena.numel:
+            raise ValueError(f"lamb: offset and numel % 64 == 0 inside the arena ({offset}, {n})")
+        lr, b1, b2, wd, gs, eps, bc1, bc2, omb1, omb2 = [hp.detach()[k] for k in range(10)]
+        parts = []          # (tensor, slice, u) of every tensor with elements in the range
+        sums = torch.zeros(st.T, 2, dtype=torch.float64, device=hp.device)
+        with torch.no_grad():
+            for k, (o, ln) in enumerate(st.ranges):
+                lo, hi = max(o, offset), min(o + ln, offset + n)
+                if lo >= hi:
+                    continue
+                sl = slice(lo, hi)
+                p, m, v = arena.master[sl], arena.exp_avg[sl], arena.exp_avg_sq[sl]
+                d = (grad_bf16[sl].float() if grad_bf16 is not None else arena.grad[sl]) * gs
+                m.mul_(b1).add_(omb1 * d)
+                v.mul_(b2).add_((omb2 * d) * d)
+                u = (m / bc1) / ((v / bc2).sqrt() + eps)
+                if float(wd) != 0:
+                    u = u + wd * p
+                sums[k, 0] = (p.double() ** 2).sum()
+                sums[k, 1] = (u.double() ** 2).sum()
+                parts.append((k, sl, u))
+            if gather is not None:
+                world, rank, allgather = gather
+                buf = st.sums(world)
+                buf[rank].copy_(sums)
+                allgather(buf)
+                sums = torch.zeros_like(sums)
+                for q in range(world):      # rank order, as lamb_trust_kernel adds them
+                    sums = sums + buf[q]
+            pn, un = sums[:, 0].sqrt(), sums[:, 1].sqrt()
+            r = torch.where((pn == 0) | (un == 0), torch.ones_like(pn), pn / un)
+            st.trust.copy_(r)
+            st.norms.copy_(torch.stack([pn, un], 1).reshape(-1))
+            for k, sl, u in parts:
+                p = arena.master[sl]
+                p.sub_((lr * st.trust[k]) * u)
+                if arena.shadow is not None:
+                    arena.shadow[sl].copy_(p)
+                if zero_grad and grad_bf16 is None:
+                    arena.grad[sl].zero_()

@@ -356,7 +356,8 @@ class ShardedSync(GradSync):
        (RCCL ncclReduceScatter in place; gloo has no reduce-scatter, so the CPU path all-reduces
        and uses its slice -- the same sums);
     2. only the owner applies SGD-momentum to its slice (1/P folded in, as usual), so the
-       momentum of the other slices is never read or written;
+       momentum of the other slices is never read or written (LAMB: between its two passes the
+       ranks all-gather their per-tensor sums, so every rank holds the same trust ratios);
     3. the updated parameters are all-gathered: the bf16 compute shadow when there is one (half
        the bytes of fp32), else the fp32 master.  With a shadow, the fp32 master is still read
        by the kernels in a few places -- every bias (forward epilogue) and the whole output
@@ -466,18 +467,29 @@ class ShardedSync(GradSync):
         self.note(3, 0, 0, self.shard, 0)
         h = self._handle()
         self._reduce_scatter(h)
+        # Sums of squares over this rank's slice (clipping: of the reduced gradient; LAMB: per
+        # tensor, of the weights and the update direction), then the P ranks' sums all-gathered
+        # bitwise and added in rank order -- every rank holds the same coefficient / trust
+        # ratios bit for bit.  ``gather``'s collective: the ``world`` equal parts of a float64
+        # buffer, in place, part ``rank`` being this rank's.
         if self.comm is not None:
-            # clipping: the sum of squares of this rank's reduced slice, then the P sums
-            # all-gathered bitwise (a double travels as two fp32 words) on the same stream and
-            # added in rank order -- every rank holds the same coefficient bit for bit
-            opt.clip(offset=self.off, numel=self.shard, gather=(
-                self.world, self.rank,
-                lambda buf: self.comm.allgather(buf.data_ptr() + 8 * self.rank, buf.data_ptr(),
-                                                2, 0, h)))
+            def allgather(buf):    # on the same stream; a double travels as two fp32 words
+                per = buf.numel() // self.world
+                self.comm.allgather(buf.data_ptr() + 8 * per * self.rank, buf.data_ptr(),
+                                    2 * per, 0, h)
+            gather = (self.world, self.rank, allgather)
+            opt.clip(offset=self.off, numel=self.shard, gather=gather)
         else:
+            def allgather(buf):    # gloo: through CPU tensors
+                host = buf.reshape(self.world, -1).cpu()
+                parts = [torch.empty_like(host[0]) for _ in range(self.world)]
+                dist.all_gather(parts, host[self.rank].contiguous(), group=self.group)
+                buf.copy_(torch.stack(parts).reshape(buf.shape))
+            gather = (self.world, self.rank, allgather)
             # the full gradient is here: the norm the all-reduce path takes, no extra collective
             opt.clip()
-        opt.apply(first, offset=self.off, numel=self.shard)
+        # (only an optimizer with per-slice sums of its own -- LAMB -- uses ``gather``)
+        opt.apply(first, offset=self.off, numel=self.shard, gather=gather)
         self._gather_params(h)
 
     def comm_only(self):

@@ -9,7 +9,7 @@ pickled ``state_dict`` it broadcasts at init (ref.py:87).  The framework writes:
   (unpadded, so it re-lays into ANY arena: another world size, with or without the sharded
   optimizer's padding), epoch, step counter, config (all tensors / plain types, so it also
   loads with ``weights_only=True``); ``optimizer`` names the optimizer that state belongs to
-  (a file without the field is SGD) and, for Adam / AdamW, ``momentum_by_name`` holds exp_avg
+  (a file without the field is SGD) and, for Adam / AdamW / LAMB, ``momentum_by_name`` holds exp_avg
   and ``exp_avg_sq_by_name`` the second moment -- the step counter restores Adam's step number.
 Writes are atomic (tmp file + rename) and done by rank 0 only.  A resume whose optimizer state
 does not fit the model -- or belongs to another optimizer than the configured one -- raises

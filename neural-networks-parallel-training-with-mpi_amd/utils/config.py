@@ -53,7 +53,7 @@ class TrainConfig:
     weight_decay: float = 0.0
     nesterov: bool = False
     # --- optimizer choice (torch.optim.Adam / AdamW semantics; momentum is ignored under them) ---
-    optimizer: str = "sgd"            # sgd | adam | adamw
+    optimizer: str = "sgd"            # sgd | adam | adamw | lamb
     beta1: float = 0.9
     beta2: float = 0.999
     eps: float = 1e-8
@@ -140,13 +140,15 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--dampening", type=float, default=0.0)
     p.add_argument("--weight_decay", type=float, default=0.0)
     p.add_argument("--nesterov", action="store_true")
-    p.add_argument("--optimizer", choices=["sgd", "adam", "adamw"], default="sgd",
+    p.add_argument("--optimizer", choices=["sgd", "adam", "adamw", "lamb"], default="sgd",
                    help="sgd: SGD-momentum (the reference's); adam / adamw: torch.optim.Adam / "
                         "AdamW semantics (--weight_decay is L2 under adam, decoupled under adamw; "
-                        "--momentum is ignored)")
-    p.add_argument("--beta1", type=float, default=0.9, help="Adam beta1 [0.9]")
-    p.add_argument("--beta2", type=float, default=0.999, help="Adam beta2 [0.999]")
-    p.add_argument("--eps", type=float, default=1e-8, help="Adam eps [1e-8]")
+                        "--momentum is ignored); lamb: Adam's moments with a trust ratio per "
+                        "weight and bias tensor, for very large batches (--weight_decay is the "
+                        "decay inside the update direction)")
+    p.add_argument("--beta1", type=float, default=0.9, help="Adam / LAMB beta1 [0.9]")
+    p.add_argument("--beta2", type=float, default=0.999, help="Adam / LAMB beta2 [0.999]")
+    p.add_argument("--eps", type=float, default=1e-8, help="Adam / LAMB eps [1e-8]")
     p.add_argument("--clip_grad_norm", type=float, default=None, metavar="G",
                    help="clip the gradient to global L2 norm G before every update "
                         "(torch.nn.utils.clip_grad_norm_ semantics, any optimizer, computed on "
@@ -282,8 +284,8 @@ def validate(cfg: TrainConfig) -> None:
         raise ValueError(cfg.dtype)
     if cfg.nesterov and (cfg.momentum <= 0 or cfg.dampening != 0):
         raise ValueError("Nesterov momentum requires a momentum and zero dampening")
-    if cfg.optimizer not in ("sgd", "adam", "adamw"):
-        raise ValueError(f"optimizer must be sgd, adam or adamw, got {cfg.optimizer!r}")
+    if cfg.optimizer not in ("sgd", "adam", "adamw", "lamb"):
+        raise ValueError(f"optimizer must be sgd, adam, adamw or lamb, got {cfg.optimizer!r}")
     if not (0.0 <= cfg.beta1 < 1.0 and 0.0 <= cfg.beta2 < 1.0):
         raise ValueError(f"beta1 and beta2 must be in [0, 1), got {cfg.beta1}, {cfg.beta2}")
     if not cfg.eps > 0:
