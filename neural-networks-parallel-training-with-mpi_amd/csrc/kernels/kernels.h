@@ -354,6 +354,22 @@ hipError_t head_eval(const void* a, int a_bf16, int lda, int rows, int in, const
                      float* logits_out, int ldl, int* pred_out, double* metrics, int accumulate,
                      float* ws, hipStream_t s);
 
+// ---- layer / RMS normalisation of hidden pre-activations, no scale or shift (norm.hip) ----
+enum Norm : int { NORM_NONE = 0, NORM_LAYER = 1, NORM_RMS = 2 };
+// z, a, dn: [rows][H] row-strided (elements), bf16 if is_bf16 else fp32; stats: [rows][2] fp32
+// (mu, rstd), dense; under NORM_RMS mu is written as 0.
+// norm_act_fwd: a = act((z - mu) * rstd), rstd = 1 / sqrt(mean((z - mu)^2) + eps); a must not
+// overlap z (the backward reads z).  norm_bwd: dn (dL/dx) is overwritten with dL/dz.
+// hipErrorInvalidValue before any launch for: norm other than LAYER / RMS, an unknown act,
+// eps < 0 or NaN, rows < 0, H < 1 or > 8192, a row stride < H, a null operand with rows > 0,
+// operands that overlap, and bf16 rows that are not H % 8 == 0 with 16-byte aligned bases and
+// strides % 8 == 0 (fp32 rows of any width and alignment run: on 16-byte loads where H % 4 == 0
+// and both operands are aligned, else on scalar loads).  rows == 0 launches nothing.
+hipError_t norm_act_fwd(const void* z, long long ldz, void* a, long long lda, float* stats,
+                        int is_bf16, int rows, int H, int norm, int act, float eps, hipStream_t s);
+hipError_t norm_bwd(void* dn, long long ldd, const void* z, long long ldz, const float* stats,
+                    int is_bf16, int rows, int H, int norm, hipStream_t s);
+
 // ---- whole tiny MLP in one launch (tiny_mlp.hip), fp32, widths <= 16, layers <= 4 ----
 struct TinyMLPDesc {
   int n_layers;

@@ -4,6 +4,8 @@ One step (per rank), replacing the reference's hot loop ``ref.py:155-211`` (Data
 ``.float()`` -> forward -> MSELoss -> autograd backward -> gather/average/send -> SGD):
 
     forward   h_i = act(h_{i-1} W_i^T + b_i)                  hidden layers (GEMM + epilogue)
+              (--norm layer | rms: z_i = h_{i-1} W_i^T + b_i, h_i = act(norm(z_i)) -- norm.hip;
+              its backward rewrites dZ_i in place right after the head / dgrad produced it)
     head      logits, loss, dlogits, dZ_{L-2}, dW_{L-1}, db   fused output layer + loss
               -> grad bucket(s) of layer L-1 ready -> all-reduce starts on the comm stream
     backward  for i = L-2 .. 0:
@@ -103,6 +105,12 @@ class MLPEngine:
         L = self.L = spec.n_layers
         w = spec.widths
         self.act, self.loss_kind = spec.activation, spec.loss
+        # hidden layers act(norm(z)) (norm.hip): no fused, grouped, row-band or one-launch tiny
+        # body takes a norm yet -- such a model runs the sequential body for every batch size
+        # (fp32 models of tiny widths on the fp32 GEMMs, as predict() does)
+        self.norm = None if spec.norm == "none" else spec.norm
+        if self.norm is not None:
+            use_tiny = overlap = False
         bf16 = dtype == torch.bfloat16
         if use_tiny is None:
             # GPU: tiny_mlp.hip; CPU: the host twin when the op set has it (ops/host_ops.py)
@@ -123,6 +131,11 @@ class MLPEngine:
         self.labels = None if mse else torch.zeros(R, dtype=torch.int64, device=dev)
         self.acts = [torch.zeros(R, w[i + 1], dtype=dtype, device=dev) for i in range(L - 1)]
         self.dzl = [torch.zeros(R, w[i + 1], dtype=dtype, device=dev) for i in range(L - 1)]
+        # with a norm: every hidden layer's pre-activations (the backward recomputes the
+        # normalised row from them) and per-row (mu, rstd) -- allocated once, like the rest
+        nh = L - 1 if self.norm is not None else 0
+        self.zpre = [torch.zeros(R, w[i + 1], dtype=dtype, device=dev) for i in range(nh)]
+        self.nstats = [torch.zeros(R, 2, dtype=torch.float32, device=dev) for i in range(nh)]
         self.dlogits = torch.zeros(R, w[-1], dtype=torch.float32, device=dev)
         self.loss_out = torch.zeros(4, dtype=torch.float32, device=dev)
         adam = optimizer != "sgd"
@@ -356,6 +369,7 @@ class MLPEngine:
         last = L - 1
         dz = self._dzl(last - 1, rows) if L > 1 else None
         self._head(h, dz)
+        self._norm_bwd(last - 1)
         self._mark("head")
         self.sync.ready(last)
         for i in range(L - 2, -1, -1):
@@ -366,8 +380,18 @@ class MLPEngine:
             if i > 0:
                 dz_next = self._dzl(i - 1, rows)
                 ops.linear_dgrad(dz, ar.compute_weight(i), self.acts[i - 1][:rows], self.act, dz_next)
+                self._norm_bwd(i - 1)
                 dz = dz_next
         self._mark("bwd")
+
+    def _norm_bwd(self, layer: int):
+        """With a norm, the head and linear_dgrad leave dL/d(normalised row) in the layer's dZ
+        buffer (they apply act' through the saved activations): turn it into dL/dz in place,
+        before the layer's weight gradient and the next dgrad read it."""
+        if self.norm is not None and layer >= 0:
+            rows = self.rows
+            self.ops.norm_bwd(self._dzl(layer, rows), self.zpre[layer][:rows],
+                              self.nstats[layer][:rows], self.norm)
 
     def _wgrad_chunks(self, i: int, dz, x_in, bf16_out: bool = False):
         """Weight gradient of layer i; a layer cut into output-row chunk buckets (Arena
@@ -408,7 +432,13 @@ class MLPEngine:
         h = x
         for i in range(self.L - 1):
             out = self.acts[i][:self.rows]
-            self.ops.linear_act(h, self.arena.compute_weight(i), self.arena.bias(i), self.act, out)
+            W, b = self.arena.compute_weight(i), self.arena.bias(i)
+            if self.norm is None:
+                self.ops.linear_act(h, W, b, self.act, out)
+            else:
+                z = self.zpre[i][:self.rows]
+                self.ops.linear_act(h, W, b, "none", z)
+                self.ops.norm_act(z, self.norm, self.act, out, self.nstats[i][:self.rows])
             h = out
         return h
 

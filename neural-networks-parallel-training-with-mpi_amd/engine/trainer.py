@@ -218,7 +218,7 @@ def init_model(j: Job, spec: MLPSpec) -> MLP:
     cfg = j.cfg
     big = spec.n_params > HOST_INIT_MAX_PARAMS and j.device.type == "cuda"
     model = reference_init(spec.widths, spec.activation, seed=cfg.seed,
-                           device=j.device if big else None)
+                           device=j.device if big else None, norm=spec.norm)
     return model
 
 
@@ -379,7 +379,7 @@ def _warn_ignored_knobs(rank: int):
 def _run(j: Job) -> TrainResult:
     cfg, rank, world = j.cfg, j.rank, j.world
     _warn_ignored_knobs(rank)
-    spec = MLPSpec(tuple(cfg.widths), cfg.activation, cfg.loss)
+    spec = MLPSpec(tuple(cfg.widths), cfg.activation, cfg.loss, cfg.norm)
     X, Y, labels, part = build_shard(j)
     # held-out validation rows: the tail of every shard (same rule on every rank, so the
     # training row counts used for loss scaling are known everywhere)

@@ -2,7 +2,8 @@
 
 :class:`MLP` keeps the reference module surface (``ref.py:35-51``): an ``nn.Module`` with a
 ``layers`` ``nn.Sequential`` of ``Linear``/activation pairs, so its state_dict keys are
-``layers.{2i}.weight`` / ``layers.{2i}.bias`` (the activation occupies the odd indices).
+``layers.{2i}.weight`` / ``layers.{2i}.bias`` (the activation -- with ``norm``, the
+parameter-free :class:`NormAct` -- occupies the odd indices).
 ``MLP()`` with no arguments is exactly the reference 2→3→1 ReLU regressor with torch's
 default init (kaiming-uniform weights, U(±1/√fan_in) biases).
 
@@ -20,6 +21,30 @@ import torch
 from torch import nn
 
 ACTIVATIONS = {"relu": nn.ReLU, "tanh": nn.Tanh}
+NORMS = ("none", "layer", "rms")
+NORM_EPS = 1e-5
+
+
+class NormAct(nn.Module):
+    """``act(norm(z))`` over the last dimension, the norm without learned scale or shift
+    (``nn.LayerNorm(H, elementwise_affine=False)`` / its RMS counterpart, eps 1e-5).  ONE module,
+    so it takes the activation's odd index in ``MLP.layers`` and, having no parameters, leaves
+    the ``state_dict`` keys of the un-normalised model exactly as they are."""
+
+    def __init__(self, norm: str, activation: str):
+        super().__init__()
+        if norm not in ("layer", "rms"):
+            raise ValueError(f"norm layer | rms, got {norm!r}")
+        self.norm = norm
+        self.act = ACTIVATIONS[activation]()
+
+    def forward(self, z):
+        if self.norm == "layer":
+            z = z - z.mean(-1, keepdim=True)
+        return self.act(z * torch.rsqrt((z * z).mean(-1, keepdim=True) + NORM_EPS))
+
+    def extra_repr(self) -> str:
+        return f"norm={self.norm}"
 
 
 @dataclass(frozen=True)
@@ -27,6 +52,7 @@ class MLPSpec:
     widths: tuple
     activation: str = "relu"
     loss: str = "mse"
+    norm: str = "none"      # none | layer | rms: per-row normalisation of every hidden layer
 
     @property
     def n_layers(self) -> int:
@@ -56,21 +82,25 @@ class MLP(nn.Module):
     """Multilayer Perceptron for regression (reference ref.py:35-51)."""
 
     def __init__(self, widths: Sequence[int] = (2, 3, 1), activation: str = "relu",
-                 device=None):
+                 norm: str = "none", device=None):
         super().__init__()
+        if norm not in NORMS:
+            raise ValueError(f"norm must be one of {NORMS}, got {norm!r}")
         widths = list(widths)
         mods: List[nn.Module] = []
         for i in range(len(widths) - 1):
             mods.append(nn.Linear(widths[i], widths[i + 1], device=device))
             if i < len(widths) - 2:
-                mods.append(ACTIVATIONS[activation]())
+                mods.append(ACTIVATIONS[activation]() if norm == "none" else
+                            NormAct(norm, activation))
         self.widths = widths
         self.activation = activation
+        self.norm = norm
         self.layers = nn.Sequential(*mods)
 
     @property
     def spec(self) -> MLPSpec:
-        return MLPSpec(tuple(self.widths), self.activation)
+        return MLPSpec(tuple(self.widths), self.activation, norm=self.norm)
 
     def linears(self) -> List[nn.Linear]:
         return [m for m in self.layers if isinstance(m, nn.Linear)]
@@ -80,7 +110,8 @@ class MLP(nn.Module):
         return self.layers(x)
 
 
-def reference_init(widths=(2, 3, 1), activation="relu", seed: int = 0, device=None) -> MLP:
+def reference_init(widths=(2, 3, 1), activation="relu", seed: int = 0, device=None,
+                   norm: str = "none") -> MLP:
     """Rank-0 init of the reference: ``torch.manual_seed(0)`` then ``MLP()`` (ref.py:69,84).
 
     With ``device=None`` the init runs on the CPU generator (bitwise the reference's values);
@@ -90,5 +121,5 @@ def reference_init(widths=(2, 3, 1), activation="relu", seed: int = 0, device=No
     dev = torch.device(device) if device is not None else torch.device("cpu")
     with torch.random.fork_rng(devices=[dev] if dev.type == "cuda" else []):
         torch.manual_seed(seed)
-        m = MLP(widths, activation, device=dev)
+        m = MLP(widths, activation, norm=norm, device=dev)
     return m

@@ -97,6 +97,20 @@ class OpSet:
         optimizer's :class:`LambState` (default: one kept with the arena)."""
         raise NotImplementedError(f"{type(self).__name__}: lamb is not supported")
 
+    # ---- layer / RMS normalisation of hidden layers (csrc/kernels/norm.hip; TorchOps: CPU path) ----
+    def norm_act(self, z, norm: str, act: str, out, stats, eps: float = 1e-5):
+        """``out = act(x)`` with ``x`` the rows of ``z`` [rows, H] normalised without scale or
+        shift: ``norm = "layer"``: ``(z - mu) * rstd``, ``rstd = 1 / sqrt(mean((z - mu)^2) + eps)``;
+        ``"rms"``: the same with ``mu = 0``.  ``stats`` (fp32 [rows, 2]) receives ``(mu, rstd)``.
+        ``out`` is another buffer than ``z``: :meth:`norm_bwd` reads ``z`` again."""
+        raise NotImplementedError(f"{type(self).__name__}: norm_act is not supported")
+
+    def norm_bwd(self, dn, z, stats, norm: str):
+        """``dn`` (the loss gradient w.r.t. ``x``) becomes the gradient w.r.t. ``z``, in place:
+        ``rstd * (dn - mean(dn) - x * mean(dn * x))`` (``"rms"``: without the ``mean(dn)`` term),
+        ``x`` recomputed from the saved ``z`` and the ``stats`` of :meth:`norm_act`."""
+        raise NotImplementedError(f"{type(self).__name__}: norm_bwd is not supported")
+
     # ---- forward-only output layer (csrc/kernels/head_eval.hip; TorchOps is the oracle) ----
     def head_eval(self, a, W, b, y=None, labels=None, loss=None, logits_out=None, pred_out=None,
                   metrics=None, accumulate: bool = False, ws=None):

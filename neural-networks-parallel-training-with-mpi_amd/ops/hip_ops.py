@@ -13,7 +13,7 @@ from ..utils.knobs import knob
 
 from .. import native
 from .base import OpSet, yes
-from .torch_ops import ACT_CODES
+from .torch_ops import ACT_CODES, NORM_CODES, NORM_EPS
 
 LOSS_CODES = {"mse": 0, "xent": 1}
 
@@ -63,6 +63,34 @@ class HipOps(OpSet):
             self.lib.linear_dgrad_f32(_p(dz), dz.stride(0), _p(W), W.stride(0), _p(a_prev),
                                       a_prev.stride(0), _p(out), out.stride(0), M, N, K,
                                       ACT_CODES[act], self.stream)
+
+    # ---------------- layer / RMS normalisation (norm.hip) ----------------
+    @staticmethod
+    def _norm_rows(what: str, norm: str, stats, *mats):
+        """(rows, H, is_bf16, row strides) of the row-strided operands of a norm launch."""
+        rows, H = mats[0].shape
+        _check(norm in NORM_CODES, f"{what}: norm layer | rms, got {norm!r}")
+        _check(all(t.dim() == 2 and tuple(t.shape) == (rows, H) and t.dtype == mats[0].dtype and
+                   (t.stride(1) == 1 or H == 1) for t in mats) and
+               mats[0].dtype in (torch.bfloat16, torch.float32),
+               f"{what}: bf16 / fp32 [rows, H] operands of one dtype, unit column stride")
+        _check(stats.dtype == torch.float32 and stats.is_contiguous() and
+               tuple(stats.shape) == (rows, 2), f"{what}: dense fp32 statistics [rows, 2]")
+        lds = [t.stride(0) if rows > 1 else max(t.stride(0), H) for t in mats]
+        return rows, H, 1 if mats[0].dtype == torch.bfloat16 else 0, lds
+
+    def norm_act(self, z, norm: str, act: str, out, stats, eps: float = NORM_EPS):
+        """See OpSet.norm_act.  One launch; what the kernel does not take (bf16 rows that are
+        not H % 8 == 0 and 16-byte aligned, H > 8192, ``out`` overlapping ``z``) raises before
+        anything is launched."""
+        rows, H, bf, (ldz, lda) = self._norm_rows("norm_act", norm, stats, z, out)
+        self.lib.norm_act_fwd(_p(z), ldz, _p(out), lda, _p(stats), bf, rows, H, NORM_CODES[norm],
+                              ACT_CODES[act], float(eps), self.stream)
+
+    def norm_bwd(self, dn, z, stats, norm: str):
+        rows, H, bf, (ldd, ldz) = self._norm_rows("norm_bwd", norm, stats, dn, z)
+        self.lib.norm_bwd(_p(dn), ldd, _p(z), ldz, _p(stats), bf, rows, H, NORM_CODES[norm],
+                          self.stream)
 
     @staticmethod
     def _check_ws(ws, need: int, what: str):

@@ -16,6 +16,8 @@ import torch
 from .base import OpSet
 
 ACT_CODES = {"none": 0, "relu": 1, "tanh": 2}
+NORM_CODES = {"layer": 1, "rms": 2}     # (kernels.h Norm; "none" is no launch at all)
+NORM_EPS = 1e-5                         # torch.nn.LayerNorm's default
 
 
 def act_fwd(z: torch.Tensor, act: str) -> torch.Tensor:
@@ -49,6 +51,26 @@ class TorchOps(OpSet):
     def linear_dgrad(self, dz, W, a_prev, act: str, out):
         g = dz.float().mm(W.float())
         out.copy_(g * act_bwd_from_out(a_prev.float(), act))
+
+    # ---- layer / RMS normalisation (the contract of OpSet.norm_act / norm_bwd in fp32 torch) ----
+    def norm_act(self, z, norm: str, act: str, out, stats, eps: float = NORM_EPS):
+        if norm not in NORM_CODES:
+            raise ValueError(f"norm_act: norm layer | rms, got {norm!r}")
+        zf = z.float()
+        mu = zf.mean(1, keepdim=True) if norm == "layer" else torch.zeros_like(zf[:, :1])
+        rstd = 1.0 / torch.sqrt(((zf - mu) ** 2).mean(1, keepdim=True) + eps)
+        out.copy_(act_fwd((zf - mu) * rstd, act))
+        stats.copy_(torch.cat([mu, rstd], 1))
+
+    def norm_bwd(self, dn, z, stats, norm: str):
+        if norm not in NORM_CODES:
+            raise ValueError(f"norm_bwd: norm layer | rms, got {norm!r}")
+        g, mu, rstd = dn.float(), stats[:, :1], stats[:, 1:2]
+        x = (z.float() - mu) * rstd
+        d = g - x * (g * x).mean(1, keepdim=True)
+        if norm == "layer":
+            d = d - g.mean(1, keepdim=True)
+        dn.copy_(rstd * d)
 
     # gW = dz^T @ x ; gb = sum(dz, 0)
     def linear_wgrad(self, dz, x, gW, gb, ws=None, out_bf16=None):

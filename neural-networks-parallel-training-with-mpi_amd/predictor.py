@@ -4,8 +4,9 @@ or a dict in memory) into outputs, loss and accuracy / mean absolute error.
 It wraps a single-rank :class:`~nnmpi_amd.engine.engine.MLPEngine` (``NoSync``): the hidden
 layers run the engine's forward GEMMs and the output layer the forward-only head
 (``csrc/kernels/head_eval.hip`` on the GPU, ``TorchOps.head_eval`` on the CPU) -- no gradient is
-computed anywhere.  The layer widths come from the weight shapes; the activation and the loss are
-not part of a ``state_dict`` and are given by the caller.
+computed anywhere.  The layer widths come from the weight shapes; the activation, the loss and
+the hidden layers' normalisation (``norm``: it has no parameters) are not part of a ``state_dict``
+and are given by the caller.
 """
 from __future__ import annotations
 
@@ -55,7 +56,8 @@ class Predictor:
 
     @classmethod
     def from_state_dict(cls, sd: dict, activation: str = "relu", loss: str = "mse",
-                        dtype: str = "fp32", device: str = "auto", batch_rows: int = 4096):
+                        dtype: str = "fp32", device: str = "auto", batch_rows: int = 4096,
+                        norm: str = "none"):
         from .engine.arena import Arena
         from .engine.engine import MLPEngine
         from .engine.trainer import cpu_ops
@@ -66,12 +68,14 @@ class Predictor:
             raise ValueError(f"activation relu | tanh and loss mse | xent, got {activation!r}, {loss!r}")
         if dtype not in ("fp32", "bf16"):
             raise ValueError(f"dtype fp32 | bf16, got {dtype!r}")
+        if norm not in ("none", "layer", "rms"):
+            raise ValueError(f"norm none | layer | rms, got {norm!r}")
         widths = _widths_of(sd)
         dev = torch.device(resolve_device(device) if device == "auto" else device)
         if dev.type == "cuda" and dev.index is None:
             dev = torch.device("cuda", torch.cuda.current_device())
         tdtype = torch.bfloat16 if dtype == "bf16" else torch.float32
-        spec = MLPSpec(tuple(widths), activation, loss)
+        spec = MLPSpec(tuple(widths), activation, loss, norm)
         arena = Arena([spec.layer_shape(i) for i in range(spec.n_layers)], dev,
                       shadow_dtype=torch.bfloat16 if tdtype == torch.bfloat16 else None)
         arena.load_state_dict({k: v.detach().to(torch.float32) for k, v in sd.items()})
@@ -88,10 +92,11 @@ class Predictor:
 
     @classmethod
     def from_checkpoint(cls, path: str, activation: str = "relu", loss: str = "mse",
-                        dtype: str = "fp32", device: str = "auto", batch_rows: int = 4096):
+                        dtype: str = "fp32", device: str = "auto", batch_rows: int = 4096,
+                        norm: str = "none"):
         from .utils.checkpoint import load_state_dict
         return cls.from_state_dict(load_state_dict(path), activation=activation, loss=loss,
-                                   dtype=dtype, device=device, batch_rows=batch_rows)
+                                   dtype=dtype, device=device, batch_rows=batch_rows, norm=norm)
 
     @property
     def widths(self):

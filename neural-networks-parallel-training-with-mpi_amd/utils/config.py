@@ -48,6 +48,7 @@ class TrainConfig:
     activation: str = "relu"          # relu | tanh
     loss: str = "mse"                 # mse | xent
     dtype: str = "fp32"               # fp32 | bf16 (compute dtype; master weights stay fp32)
+    norm: str = "none"                # none | layer | rms: hidden layers become act(norm(z))
     # --- optimizer extras (torch.optim.SGD semantics) ---
     dampening: float = 0.0
     weight_decay: float = 0.0
@@ -137,6 +138,12 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--activation", choices=["relu", "tanh"], default=None)
     p.add_argument("--loss", choices=["mse", "xent"], default=None)
     p.add_argument("--dtype", choices=["fp32", "bf16"], default=None)
+    p.add_argument("--norm", choices=["none", "layer", "rms"], default="none",
+                   help="normalise every hidden layer's pre-activations per row before the "
+                        "activation: layer = torch.nn.LayerNorm(H, elementwise_affine=False), rms "
+                        "= its RMS counterpart (eps 1e-5, no learned scale or shift, so "
+                        "parameters, checkpoints and state_dict keys are unchanged).  Such a "
+                        "model runs the sequential schedule (as --no_overlap) [none]")
     p.add_argument("--dampening", type=float, default=0.0)
     p.add_argument("--weight_decay", type=float, default=0.0)
     p.add_argument("--nesterov", action="store_true")
@@ -282,6 +289,8 @@ def validate(cfg: TrainConfig) -> None:
         raise ValueError("xent needs >= 2 output classes")
     if cfg.dtype not in ("fp32", "bf16"):
         raise ValueError(cfg.dtype)
+    if cfg.norm not in ("none", "layer", "rms"):
+        raise ValueError(f"norm must be none, layer or rms, got {cfg.norm!r}")
     if cfg.nesterov and (cfg.momentum <= 0 or cfg.dampening != 0):
         raise ValueError("Nesterov momentum requires a momentum and zero dampening")
     if cfg.optimizer not in ("sgd", "adam", "adamw", "lamb"):
