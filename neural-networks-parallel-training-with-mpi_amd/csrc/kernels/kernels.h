@@ -370,6 +370,30 @@ hipError_t norm_act_fwd(const void* z, long long ldz, void* a, long long lda, fl
 hipError_t norm_bwd(void* dn, long long ldd, const void* z, long long ldz, const float* stats,
                     int is_bf16, int rows, int H, int norm, hipStream_t s);
 
+// ---- inverted dropout of hidden activations, Philox4x32-10 mask never stored (dropout.hip) ----
+// a, d, dd: [rows][H] row-strided (elements), bf16 if is_bf16 else fp32.  state: int32[4] in
+// device memory = (seed lo32, seed hi32, pass, unused), read by the kernels at run time.  Logical
+// element e = r * H + c takes word e & 3 of the Philox call with counter (g lo32, g hi32, pass,
+// (rank << 8) | layer), g = e >> 2, key (seed lo32, seed hi32); it is kept iff word >= T.
+// dropout_fwd: d = kept ? float(a) * scale : +0 (one fp32 multiply, rounded once to the element
+// type); d must not overlap a.  dropout_bwd: dd = kept ? float(dd) * scale * act'(a) : +0 in
+// place, a the UNDROPPED activation (relu: a > 0, none: 1, both on the fp32 product; tanh:
+// 1 - a^2, the whole product formed in double and rounded once).
+// dropout_tick: state[2] += 1 (one thread).
+// hipErrorInvalidValue before any launch for: an unknown act, rows < 0, H < 1 or > 8192,
+// rows * H >= 2^34, a row stride < H, layer outside 0..255, rank outside 0..2^24-1, a scale that
+// is not finite and >= 1, a null operand with rows > 0, operands that overlap, and bf16 rows that
+// are not H % 8 == 0 with 16-byte aligned bases and strides % 8 == 0 (fp32 rows of any width and
+// alignment run: 16-byte accesses where H % 4 == 0 and both operands are aligned, else one
+// element per access -- the mask is the same either way).  rows == 0 launches nothing.
+hipError_t dropout_fwd(const void* a, long long lda, void* d, long long ldd, const int* state,
+                       int is_bf16, int rows, int H, unsigned T, float scale, int layer, int rank,
+                       hipStream_t s);
+hipError_t dropout_bwd(void* dd, long long ldd, const void* a, long long lda, const int* state,
+                       int is_bf16, int rows, int H, unsigned T, float scale, int act, int layer,
+                       int rank, hipStream_t s);
+hipError_t dropout_tick(int* state, hipStream_t s);
+
 // ---- whole tiny MLP in one launch (tiny_mlp.hip), fp32, widths <= 16, layers <= 4 ----
 struct TinyMLPDesc {
   int n_layers;

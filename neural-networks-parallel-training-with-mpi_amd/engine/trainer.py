@@ -218,7 +218,8 @@ def init_model(j: Job, spec: MLPSpec) -> MLP:
     cfg = j.cfg
     big = spec.n_params > HOST_INIT_MAX_PARAMS and j.device.type == "cuda"
     model = reference_init(spec.widths, spec.activation, seed=cfg.seed,
-                           device=j.device if big else None, norm=spec.norm)
+                           device=j.device if big else None, norm=spec.norm,
+                           dropout=spec.dropout)
     return model
 
 
@@ -379,7 +380,7 @@ def _warn_ignored_knobs(rank: int):
 def _run(j: Job) -> TrainResult:
     cfg, rank, world = j.cfg, j.rank, j.world
     _warn_ignored_knobs(rank)
-    spec = MLPSpec(tuple(cfg.widths), cfg.activation, cfg.loss, cfg.norm)
+    spec = MLPSpec(tuple(cfg.widths), cfg.activation, cfg.loss, cfg.norm, float(cfg.dropout))
     X, Y, labels, part = build_shard(j)
     # held-out validation rows: the tail of every shard (same rule on every rank, so the
     # training row counts used for loss scaling are known everywhere)
@@ -421,8 +422,10 @@ def _run(j: Job) -> TrainResult:
                     dampening=cfg.dampening, weight_decay=cfg.weight_decay,
                     nesterov=cfg.nesterov, use_graph=cfg.graph, overlap=cfg.overlap,
                     optimizer=cfg.optimizer, beta1=cfg.beta1, beta2=cfg.beta2, eps=cfg.eps,
-                    clip_grad_norm=cfg.clip_grad_norm)
+                    clip_grad_norm=cfg.clip_grad_norm, dropout_seed=cfg.seed, dropout_rank=rank)
     clipping = cfg.clip_grad_norm is not None
+    # --dropout: what a checkpoint carries on top (nothing without the flag)
+    drop_state = (lambda: (eng.dropout_step, eng.dropout_seed)) if spec.dropout else (lambda: None)
 
     def clip_metrics(norm=None, coef=None) -> dict:
         """--clip_grad_norm: the pre-clip norm of the averaged gradient and the coefficient of
@@ -436,6 +439,9 @@ def _run(j: Job) -> TrainResult:
         res.clip_coefs.append(m["clip_coef"])
         return m
     eng.steps_done = steps_done      # (also the optimizer's device-side step number)
+    if cfg.resume and spec.dropout:
+        # the masks of the uninterrupted run: its pass number and key (a file without: pass 0)
+        eng.dropout_step, eng.dropout_seed = ckpt.load_dropout_state(cfg.resume, cfg.seed)
     if cfg.profile_steps:
         from ..utils.metrics import EventTimer
         eng.timer = EventTimer(j.device.type)
@@ -632,7 +638,8 @@ def _run(j: Job) -> TrainResult:
             if cfg.checkpoint and cfg.checkpoint_every and (epoch + 1) % cfg.checkpoint_every == 0:
                 _gather_state(eng, sync)
                 if rank == 0:
-                    ckpt.save(cfg.checkpoint, arena, epoch + 1, eng.steps_done, cfg)
+                    ckpt.save(cfg.checkpoint, arena, epoch + 1, eng.steps_done, cfg,
+                              dropout=drop_state())
                 j.pg.barrier()
         eng.synchronize()
         res.steps = eng.steps_done
@@ -656,7 +663,7 @@ def _run(j: Job) -> TrainResult:
                           comm_bus_GBps=comm_bus_gbps(cvol["wire_bytes_per_rank"], comm_ms))
         _gather_state(eng, sync)
         if cfg.checkpoint and rank == 0:
-            ckpt.save(cfg.checkpoint, arena, cfg.nepochs, eng.steps_done, cfg)
+            ckpt.save(cfg.checkpoint, arena, cfg.nepochs, eng.steps_done, cfg, dropout=drop_state())
         res.final_params = arena.flat_params_forward_order().detach().cpu().clone()
         res.state_dict = {k: v.cpu() for k, v in arena.state_dict().items()}
         j.pg.barrier()

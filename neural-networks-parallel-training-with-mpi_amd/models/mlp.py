@@ -3,7 +3,8 @@
 :class:`MLP` keeps the reference module surface (``ref.py:35-51``): an ``nn.Module`` with a
 ``layers`` ``nn.Sequential`` of ``Linear``/activation pairs, so its state_dict keys are
 ``layers.{2i}.weight`` / ``layers.{2i}.bias`` (the activation -- with ``norm``, the
-parameter-free :class:`NormAct` -- occupies the odd indices).
+parameter-free :class:`NormAct`; with ``dropout``, either inside one :class:`ActDrop` --
+occupies the odd indices).
 ``MLP()`` with no arguments is exactly the reference 2→3→1 ReLU regressor with torch's
 default init (kaiming-uniform weights, U(±1/√fan_in) biases).
 
@@ -47,12 +48,27 @@ class NormAct(nn.Module):
         return f"norm={self.norm}"
 
 
+class ActDrop(nn.Module):
+    """The hidden layer's activation (or :class:`NormAct`) followed by ``nn.Dropout(p)``, as ONE
+    module at the activation's odd index: no parameters, so the ``state_dict`` keys stay those
+    of the plain model.  ``eval()`` switches the dropout off, as for any torch module."""
+
+    def __init__(self, act: nn.Module, p: float):
+        super().__init__()
+        self.act = act
+        self.drop = nn.Dropout(p)
+
+    def forward(self, z):
+        return self.drop(self.act(z))
+
+
 @dataclass(frozen=True)
 class MLPSpec:
     widths: tuple
     activation: str = "relu"
     loss: str = "mse"
     norm: str = "none"      # none | layer | rms: per-row normalisation of every hidden layer
+    dropout: float = 0.0    # 0 <= p < 1: drop probability of every hidden layer's activations
 
     @property
     def n_layers(self) -> int:
@@ -82,25 +98,28 @@ class MLP(nn.Module):
     """Multilayer Perceptron for regression (reference ref.py:35-51)."""
 
     def __init__(self, widths: Sequence[int] = (2, 3, 1), activation: str = "relu",
-                 norm: str = "none", device=None):
+                 norm: str = "none", device=None, dropout: float = 0.0):
         super().__init__()
         if norm not in NORMS:
             raise ValueError(f"norm must be one of {NORMS}, got {norm!r}")
+        if not 0.0 <= dropout < 1.0:
+            raise ValueError(f"dropout must be in [0, 1), got {dropout!r}")
         widths = list(widths)
         mods: List[nn.Module] = []
         for i in range(len(widths) - 1):
             mods.append(nn.Linear(widths[i], widths[i + 1], device=device))
             if i < len(widths) - 2:
-                mods.append(ACTIVATIONS[activation]() if norm == "none" else
-                            NormAct(norm, activation))
+                act = ACTIVATIONS[activation]() if norm == "none" else NormAct(norm, activation)
+                mods.append(act if dropout == 0.0 else ActDrop(act, dropout))
         self.widths = widths
         self.activation = activation
         self.norm = norm
+        self.dropout = float(dropout)
         self.layers = nn.Sequential(*mods)
 
     @property
     def spec(self) -> MLPSpec:
-        return MLPSpec(tuple(self.widths), self.activation, norm=self.norm)
+        return MLPSpec(tuple(self.widths), self.activation, norm=self.norm, dropout=self.dropout)
 
     def linears(self) -> List[nn.Linear]:
         return [m for m in self.layers if isinstance(m, nn.Linear)]
@@ -111,7 +130,7 @@ class MLP(nn.Module):
 
 
 def reference_init(widths=(2, 3, 1), activation="relu", seed: int = 0, device=None,
-                   norm: str = "none") -> MLP:
+                   norm: str = "none", dropout: float = 0.0) -> MLP:
     """Rank-0 init of the reference: ``torch.manual_seed(0)`` then ``MLP()`` (ref.py:69,84).
 
     With ``device=None`` the init runs on the CPU generator (bitwise the reference's values);
@@ -121,5 +140,5 @@ def reference_init(widths=(2, 3, 1), activation="relu", seed: int = 0, device=No
     dev = torch.device(device) if device is not None else torch.device("cpu")
     with torch.random.fork_rng(devices=[dev] if dev.type == "cuda" else []):
         torch.manual_seed(seed)
-        m = MLP(widths, activation, norm=norm, device=dev)
+        m = MLP(widths, activation, norm=norm, device=dev, dropout=dropout)
     return m

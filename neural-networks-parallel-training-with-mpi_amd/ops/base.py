@@ -111,6 +111,30 @@ class OpSet:
         ``x`` recomputed from the saved ``z`` and the ``stats`` of :meth:`norm_act`."""
         raise NotImplementedError(f"{type(self).__name__}: norm_bwd is not supported")
 
+    # ---- dropout of hidden activations (csrc/kernels/dropout.hip; TorchOps: CPU path, oracle) ----
+    # The mask is never stored: logical element e = r * H + c of a [rows, H] operand takes word
+    # e & 3 of the Philox4x32-10 call with counter (g lo32, g hi32, pass, (rank << 8) | layer),
+    # g = e >> 2, and key (seed lo32, seed hi32); it is kept iff word >= T.  ``state`` is the
+    # int32[4] tensor (seed lo32, seed hi32, pass, 0) of torch_ops.dropout_state, read where the
+    # op runs; (T, scale) come from torch_ops.dropout_consts(p).
+    def dropout(self, a, out, state, p: float, layer: int, rank: int):
+        """``out = float(a) * scale`` where kept (one fp32 multiply, rounded once to the element
+        type), ``+0`` where dropped.  ``out`` is another buffer than ``a``: the backward reads the
+        undropped ``a``."""
+        raise NotImplementedError(f"{type(self).__name__}: dropout is not supported")
+
+    def dropout_bwd(self, dd, a, state, p: float, act: str, layer: int, rank: int):
+        """``dd`` (the loss gradient w.r.t. the dropped activations) becomes the gradient w.r.t.
+        the activation's input, in place: with ``g = float(dd) * scale``, ``relu``: ``g`` where
+        ``a > 0`` else 0; ``none``: ``g``; ``tanh``: ``dd * scale * (1 - a^2)`` formed in double
+        and rounded once (three fp32 roundings stray up to 1.9 ulp); ``+0`` where dropped.
+        ``a`` is the UNDROPPED activation :meth:`dropout` read; the mask is regenerated."""
+        raise NotImplementedError(f"{type(self).__name__}: dropout_bwd is not supported")
+
+    def dropout_tick(self, state):
+        """``state[2] += 1`` where the ops run: the next pass draws another mask."""
+        raise NotImplementedError(f"{type(self).__name__}: dropout_tick is not supported")
+
     # ---- forward-only output layer (csrc/kernels/head_eval.hip; TorchOps is the oracle) ----
     def head_eval(self, a, W, b, y=None, labels=None, loss=None, logits_out=None, pred_out=None,
                   metrics=None, accumulate: bool = False, ws=None):

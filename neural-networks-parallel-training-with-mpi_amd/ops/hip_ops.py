@@ -13,7 +13,7 @@ from ..utils.knobs import knob
 
 from .. import native
 from .base import OpSet, yes
-from .torch_ops import ACT_CODES, NORM_CODES, NORM_EPS
+from .torch_ops import ACT_CODES, NORM_CODES, NORM_EPS, dropout_consts
 
 LOSS_CODES = {"mse": 0, "xent": 1}
 
@@ -91,6 +91,39 @@ class HipOps(OpSet):
         rows, H, bf, (ldd, ldz) = self._norm_rows("norm_bwd", norm, stats, dn, z)
         self.lib.norm_bwd(_p(dn), ldd, _p(z), ldz, _p(stats), bf, rows, H, NORM_CODES[norm],
                           self.stream)
+
+    # ---------------- dropout (dropout.hip) ----------------
+    @staticmethod
+    def _drop_rows(what: str, state, layer: int, rank: int, *mats):
+        """(rows, H, is_bf16, row strides) of the row-strided operands of a dropout launch."""
+        rows, H = mats[0].shape
+        _check(all(t.dim() == 2 and tuple(t.shape) == (rows, H) and t.dtype == mats[0].dtype and
+                   (t.stride(1) == 1 or H == 1) for t in mats) and
+               mats[0].dtype in (torch.bfloat16, torch.float32),
+               f"{what}: bf16 / fp32 [rows, H] operands of one dtype, unit column stride")
+        _check(state.dtype == torch.int32 and state.is_contiguous() and state.numel() == 4 and
+               state.device == mats[0].device, f"{what}: int32[4] state on the operands' device")
+        _check(0 <= layer < 256 and 0 <= rank < 2 ** 24, f"{what}: layer < 256, rank < 2^24")
+        lds = [t.stride(0) if rows > 1 else max(t.stride(0), H) for t in mats]
+        return rows, H, 1 if mats[0].dtype == torch.bfloat16 else 0, lds
+
+    def dropout(self, a, out, state, p: float, layer: int, rank: int):
+        """See OpSet.dropout.  One launch; what the kernel does not take (bf16 rows that are not
+        H % 8 == 0 and 16-byte aligned, H > 8192, ``out`` overlapping ``a``) raises before
+        anything is launched."""
+        rows, H, bf, (lda, ldd) = self._drop_rows("dropout", state, layer, rank, a, out)
+        T, scale = dropout_consts(p)
+        self.lib.dropout_fwd(_p(a), lda, _p(out), ldd, _p(state), bf, rows, H, T, scale, layer,
+                             rank, self.stream)
+
+    def dropout_bwd(self, dd, a, state, p: float, act: str, layer: int, rank: int):
+        rows, H, bf, (ldd, lda) = self._drop_rows("dropout_bwd", state, layer, rank, dd, a)
+        T, scale = dropout_consts(p)
+        self.lib.dropout_bwd(_p(dd), ldd, _p(a), lda, _p(state), bf, rows, H, T, scale,
+                             ACT_CODES[act], layer, rank, self.stream)
+
+    def dropout_tick(self, state):
+        self.lib.dropout_tick(_p(state), self.stream)
 
     @staticmethod
     def _check_ws(ws, need: int, what: str):

@@ -20,6 +20,55 @@ NORM_CODES = {"layer": 1, "rms": 2}     # (kernels.h Norm; "none" is no launch a
 NORM_EPS = 1e-5                         # torch.nn.LayerNorm's default
 
 
+# ---- dropout: the Philox4x32-10 mask of csrc/kernels/dropout.hip, bit for bit, in numpy ----
+PHILOX_M = (0xD2511F53, 0xCD9E8D57)     # multipliers
+PHILOX_W = (0x9E3779B9, 0xBB67AE85)     # Weyl key increments
+
+
+def philox4x32_10(ctr, key):
+    """Philox4x32-10 (Salmon et al., SC'11): ``ctr`` four and ``key`` two arrays (or ints) of
+    32-bit values -> four uint64 arrays holding the 32-bit output words."""
+    import numpy as np
+    u, lo32 = np.uint64, np.uint64(0xFFFFFFFF)
+    c = [np.asarray(x, dtype=u) for x in ctr]
+    k = [np.asarray(x, dtype=u) for x in key]
+    for _ in range(10):
+        p0, p1 = u(PHILOX_M[0]) * c[0], u(PHILOX_M[1]) * c[2]      # 32 x 32 -> 64 bits: exact
+        c = [(p1 >> u(32)) ^ c[1] ^ k[0], p1 & lo32, (p0 >> u(32)) ^ c[3] ^ k[1], p0 & lo32]
+        k = [(k[0] + u(PHILOX_W[0])) & lo32, (k[1] + u(PHILOX_W[1])) & lo32]
+    return c
+
+
+def dropout_consts(p: float):
+    """(T, scale) of drop probability ``p``: an element is kept iff its mask word >= T =
+    min(2^32 - 1, round(p * 2^32)); kept values are multiplied by scale = float32(1 / (1 - p)).
+    Both op sets take them from here."""
+    import numpy as np
+    if not 0.0 < p < 1.0:
+        raise ValueError(f"dropout: 0 < p < 1, got {p}")
+    return min(2 ** 32 - 1, int(round(p * 2 ** 32))), float(np.float32(1.0 / (1.0 - p)))
+
+
+def dropout_state(seed: int, step: int, device) -> torch.Tensor:
+    """The int32[4] device state the dropout kernels read: (seed lo32, seed hi32, pass, 0)."""
+    words = [seed & 0xFFFFFFFF, (seed >> 32) & 0xFFFFFFFF, step & 0xFFFFFFFF, 0]
+    return torch.tensor([w - 2 ** 32 if w >= 2 ** 31 else w for w in words], dtype=torch.int32,
+                        device=device)
+
+
+def dropout_keep(state, p: float, layer: int, rank: int, rows: int, H: int) -> torch.Tensor:
+    """bool [rows, H]: the kept elements.  Logical element e = r * H + c takes word e & 3 of the
+    call with counter (g lo32, g hi32, pass, (rank << 8) | layer), g = e >> 2, key = the seed."""
+    import numpy as np
+    lo, hi, step = (int(v) & 0xFFFFFFFF for v in state[:3].tolist())
+    n = rows * H
+    g = np.arange((n + 3) // 4, dtype=np.uint64)
+    words = philox4x32_10((g & np.uint64(0xFFFFFFFF), g >> np.uint64(32), step,
+                           ((rank << 8) | layer) & 0xFFFFFFFF), (lo, hi))
+    flat = np.stack(words, 1).reshape(-1)[:n]
+    return torch.from_numpy(flat >= np.uint64(dropout_consts(p)[0])).reshape(rows, H)
+
+
 def act_fwd(z: torch.Tensor, act: str) -> torch.Tensor:
     if act == "relu":
         return torch.relu(z)
@@ -71,6 +120,25 @@ class TorchOps(OpSet):
         if norm == "layer":
             d = d - g.mean(1, keepdim=True)
         dn.copy_(rstd * d)
+
+    # ---- dropout (the contract of OpSet.dropout / dropout_bwd; the mask is the kernels' own) ----
+    def dropout(self, a, out, state, p: float, layer: int, rank: int):
+        keep = dropout_keep(state, p, layer, rank, *a.shape).to(a.device)
+        scale = torch.tensor(dropout_consts(p)[1], dtype=torch.float32, device=a.device)
+        out.copy_(torch.where(keep, a.float() * scale, torch.zeros((), device=a.device)))
+
+    def dropout_bwd(self, dd, a, state, p: float, act: str, layer: int, rank: int):
+        keep = dropout_keep(state, p, layer, rank, *dd.shape).to(dd.device)
+        zero = torch.zeros((), device=dd.device)
+        g = dd.float() * torch.tensor(dropout_consts(p)[1], dtype=torch.float32, device=dd.device)
+        if act == "relu":
+            g = torch.where(a.float() > 0, g, zero)
+        elif act == "tanh":
+            g = (dd.double() * dropout_consts(p)[1] * (1.0 - a.double() ** 2)).float()
+        dd.copy_(torch.where(keep, g, zero))
+
+    def dropout_tick(self, state):
+        state[2] += 1
 
     # gW = dz^T @ x ; gb = sum(dz, 0)
     def linear_wgrad(self, dz, x, gW, gb, ws=None, out_bf16=None):

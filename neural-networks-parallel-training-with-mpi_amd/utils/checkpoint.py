@@ -10,7 +10,9 @@ pickled ``state_dict`` it broadcasts at init (ref.py:87).  The framework writes:
   optimizer's padding), epoch, step counter, config (all tensors / plain types, so it also
   loads with ``weights_only=True``); ``optimizer`` names the optimizer that state belongs to
   (a file without the field is SGD) and, for Adam / AdamW / LAMB, ``momentum_by_name`` holds exp_avg
-  and ``exp_avg_sq_by_name`` the second moment -- the step counter restores Adam's step number.
+  and ``exp_avg_sq_by_name`` the second moment -- the step counter restores Adam's step number;
+  with ``--dropout`` (only then) ``dropout_step`` / ``dropout_seed``: the mask generator's pass
+  number and key, so a resumed run draws the masks the uninterrupted one would.
 Writes are atomic (tmp file + rename) and done by rank 0 only.  A resume whose optimizer state
 does not fit the model -- or belongs to another optimizer than the configured one -- raises
 instead of silently restarting the state from zero.
@@ -31,7 +33,10 @@ def _atomic_save(obj, path: str):
     os.replace(tmp, path)
 
 
-def save(path: str, arena, epoch: int, steps: int, cfg=None):
+def save(path: str, arena, epoch: int, steps: int, cfg=None, dropout=None):
+    """``dropout``: ``(dropout_step, seed)`` of an engine with dropout on, else None -- the
+    fields (and the config's ``dropout`` entry) are written only then, so the files of every
+    other configuration are byte for byte what they were before the option existed."""
     sd = {k: v.detach().cpu() for k, v in arena.state_dict().items()}
     _atomic_save(sd, path)
     optimizer = getattr(cfg, "optimizer", "sgd") if cfg is not None else "sgd"
@@ -43,8 +48,11 @@ def save(path: str, arena, epoch: int, steps: int, cfg=None):
         "steps": int(steps),
         "numel": int(arena.numel),
         "config": {k: (v if isinstance(v, (int, float, str, bool, type(None))) else str(v))
-                   for k, v in (dataclasses.asdict(cfg).items() if cfg is not None else [])},
+                   for k, v in (dataclasses.asdict(cfg).items() if cfg is not None else [])
+                   if k != "dropout" or dropout is not None},
     }
+    if dropout is not None:
+        train["dropout_step"], train["dropout_seed"] = int(dropout[0]), int(dropout[1])
     if optimizer != "sgd":
         train["exp_avg_sq_by_name"] = {
             k: v.detach().cpu().clone()
@@ -75,6 +83,15 @@ def _load_views(tp: str, what: str, saved, views):
             raise ValueError(f"{tp}: {what} of {k} has shape {tuple(saved[k].shape)}, "
                              f"the model's is {tuple(v.shape)}")
         v.copy_(saved[k].to(v.device))
+
+
+def load_dropout_state(path: str, seed: int = 0):
+    """(dropout_step, seed) of ``<path>.train``; a missing file or field: pass 0, ``seed``."""
+    tp = path + ".train"
+    if not os.path.exists(tp):
+        return 0, seed
+    st = torch.load(tp, map_location="cpu", weights_only=True)
+    return int(st.get("dropout_step", 0)), int(st.get("dropout_seed", seed))
 
 
 def load_training_state(path: str, arena, optimizer: str = "sgd"):

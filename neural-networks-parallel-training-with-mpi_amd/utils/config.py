@@ -49,6 +49,7 @@ class TrainConfig:
     loss: str = "mse"                 # mse | xent
     dtype: str = "fp32"               # fp32 | bf16 (compute dtype; master weights stay fp32)
     norm: str = "none"                # none | layer | rms: hidden layers become act(norm(z))
+    dropout: float = 0.0              # 0 <= p < 1: drop probability of hidden activations
     # --- optimizer extras (torch.optim.SGD semantics) ---
     dampening: float = 0.0
     weight_decay: float = 0.0
@@ -144,6 +145,13 @@ def build_parser() -> argparse.ArgumentParser:
                         "= its RMS counterpart (eps 1e-5, no learned scale or shift, so "
                         "parameters, checkpoints and state_dict keys are unchanged).  Such a "
                         "model runs the sequential schedule (as --no_overlap) [none]")
+    p.add_argument("--dropout", type=float, default=0.0, metavar="P",
+                   help="drop every hidden activation with probability P during training and "
+                        "scale the kept ones by 1 / (1 - P) (inverted dropout; evaluation and "
+                        "prediction run without it).  The mask is a counter-based Philox4x32-10 "
+                        "function of (--seed, pass number, rank, layer, element), regenerated in "
+                        "the backward, never stored.  Such a model runs the sequential schedule "
+                        "(as --no_overlap) [0: off]")
     p.add_argument("--dampening", type=float, default=0.0)
     p.add_argument("--weight_decay", type=float, default=0.0)
     p.add_argument("--nesterov", action="store_true")
@@ -291,6 +299,8 @@ def validate(cfg: TrainConfig) -> None:
         raise ValueError(cfg.dtype)
     if cfg.norm not in ("none", "layer", "rms"):
         raise ValueError(f"norm must be none, layer or rms, got {cfg.norm!r}")
+    if not 0.0 <= float(cfg.dropout) < 1.0:    # (also NaN)
+        raise ValueError(f"dropout must be in [0, 1), got {cfg.dropout!r}")
     if cfg.nesterov and (cfg.momentum <= 0 or cfg.dampening != 0):
         raise ValueError("Nesterov momentum requires a momentum and zero dampening")
     if cfg.optimizer not in ("sgd", "adam", "adamw", "lamb"):
