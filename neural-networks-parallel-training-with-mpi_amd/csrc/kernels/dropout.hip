@@ -14,8 +14,8 @@
 //                saved activation.  With g = float(dd) * scale (fp32): relu a > 0 ? g : 0, none g;
 //                tanh: dd * scale * (1 - a^2) formed in double (fma(-a, a, 1)) and rounded once.
 //
-// Work split.  A row is cut into CHUNKS of 16 bytes (8 bf16 / 4 fp32; 1 fp32 in the scalar form
-// that takes fp32 rows of any width and alignment).  H is a multiple of the chunk, so chunk q of
+// Work split.  A row is cut into the chunks of rowwise.h (8 bf16 / 4 fp32, or 1 fp32 in the
+// scalar form).  H is a multiple of the chunk, so chunk q of
 // the matrix holds the logical elements q * VEC ..: a chunk is exactly two (bf16), one (fp32) or
 // a quarter (scalar: the call of g = q >> 2, word q & 3 -- a call group may straddle two rows)
 // Philox calls, and the counter needs q alone.  Nothing is reduced over a row, so the grid is a
@@ -25,7 +25,7 @@
 // per trip and issues all of their loads before the first Philox round, so the integer work of
 // chunk k (10 rounds = 20 mul_hi / mul_lo pairs per call) runs under the latency of the rest.
 // The grid depends on the element count alone.  64-bit element indices; rows * H < 2^34.
-#include "common.h"
+#include "rowwise.h"
 
 namespace nnmpi {
 namespace {
@@ -33,7 +33,6 @@ namespace {
 constexpr int DROP_THREADS = 256;
 constexpr int DROP_INFLIGHT = 4;     // chunks per thread and trip
 constexpr int DROP_MAX_BLOCKS = 2048;   // 8 blocks on each of 256 CUs
-constexpr int DROP_MAX_H = 8192;
 constexpr long long DROP_MAX_ELEMS = 1ll << 34;
 
 constexpr uint32_t PHILOX_M0 = 0xD2511F53u, PHILOX_M1 = 0xCD9E8D57u;
@@ -55,18 +54,6 @@ __device__ __forceinline__ void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t
   }
   w[0] = c0; w[1] = c1; w[2] = c2; w[3] = c3;
 }
-
-template <typename T, int VEC> struct DropVec;
-template <> struct DropVec<bf16, 8> { typedef bf16x8 type; };
-template <> struct DropVec<float, 4> { typedef f32x4 type; };
-template <> struct DropVec<float, 1> { typedef float type; };
-
-__device__ __forceinline__ float elem(const bf16x8& v, int i) { return (float)v[i]; }
-__device__ __forceinline__ float elem(const f32x4& v, int i) { return v[i]; }
-__device__ __forceinline__ float elem(const float& v, int) { return v; }
-__device__ __forceinline__ void put(bf16x8& v, int i, float x) { v[i] = (bf16)x; }
-__device__ __forceinline__ void put(f32x4& v, int i, float x) { v[i] = x; }
-__device__ __forceinline__ void put(float& v, int, float x) { v = x; }
 
 // The VEC mask words of chunk q.
 template <int VEC>
@@ -100,7 +87,7 @@ __global__ __launch_bounds__(DROP_THREADS) void dropout_kernel(
     const T* x, long long ldx, const T* __restrict__ y, long long ldy, T* out, long long ldo,
     const int* __restrict__ state, unsigned long long n, unsigned C, unsigned long long srow, unsigned scol, uint32_t thr, float scale, uint32_t tag) {
 #pragma clang fp contract(off)
-  typedef typename DropVec<T, VEC>::type V;
+  typedef typename RowVec<T, VEC>::type V;
   const uint32_t k0 = (uint32_t)state[0], k1 = (uint32_t)state[1], pass = (uint32_t)state[2];
   const unsigned tid = blockIdx.x * DROP_THREADS + threadIdx.x;
   const unsigned long long stride = (unsigned long long)gridDim.x * DROP_THREADS;
@@ -155,30 +142,10 @@ __global__ __launch_bounds__(DROP_THREADS) void dropout_kernel(
 
 __global__ void dropout_tick_kernel(int* __restrict__ state) { state[2] += 1; }
 
-bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
-bool overlap(const void* p0, long long ld0, const void* p1, long long ld1, int rows, int H, int es) {
-  const char* a = static_cast<const char*>(p0);
-  const char* b = static_cast<const char*>(p1);
-  const long long na = ((rows - 1) * ld0 + H) * es, nb = ((rows - 1) * ld1 + H) * es;
-  return a < b + nb && b < a + na;
-}
-
-// The checks both launchers share; *vec = the chunk width to run: 8 (bf16), 4 / 1 (fp32).
-hipError_t drop_check(int is_bf16, const void* p0, long long ld0, const void* p1, long long ld1,
-                      const int* state, int rows, int H, float scale, int layer, int rank,
-                      int* vec) {
-  if (rows < 0 || H <= 0 || H > DROP_MAX_H || ld0 < H || ld1 < H) return hipErrorInvalidValue;
-  if ((long long)rows * H >= DROP_MAX_ELEMS) return hipErrorInvalidValue;
-  if (layer < 0 || layer > 255 || rank < 0 || rank >= (1 << 24)) return hipErrorInvalidValue;
-  if (!(scale >= 1.f) || scale * 0.f != 0.f) return hipErrorInvalidValue;   // (NaN, inf)
-  if (rows == 0) return hipSuccess;
-  if (!p0 || !p1 || !state) return hipErrorInvalidValue;
-  if (overlap(p0, ld0, p1, ld1, rows, H, is_bf16 ? 2 : 4)) return hipErrorInvalidValue;
-  const int v = is_bf16 ? 8 : 4;
-  const bool ok = H % v == 0 && ld0 % v == 0 && ld1 % v == 0 && aligned16(p0) && aligned16(p1);
-  *vec = ok ? v : (is_bf16 ? 0 : 1);
-  return *vec == 0 ? hipErrorInvalidValue : hipSuccess;
+// dropout's own arguments (the operands: row_check, rowwise.h)
+bool drop_args_ok(int rows, int H, float scale, int layer, int rank) {
+  return (long long)rows * H < DROP_MAX_ELEMS && layer >= 0 && layer <= 255 && rank >= 0 &&
+         rank < (1 << 24) && scale >= 1.f && scale * 0.f == 0.f;   // (NaN, inf: refused)
 }
 
 template <typename T, int VEC, bool BWD, int ACT>
@@ -198,41 +165,34 @@ hipError_t drop_launch(const void* x, long long ldx, const void* y, long long ld
   return hipGetLastError();
 }
 
-template <bool BWD, int ACT, typename... A>
-hipError_t drop_pick_vec(int vec, A... a) {
-  if (vec == 8) return drop_launch<bf16, 8, BWD, ACT>(a...);
-  if (vec == 4) return drop_launch<float, 4, BWD, ACT>(a...);
-  return drop_launch<float, 1, BWD, ACT>(a...);
-}
-
 }  // namespace
 
 hipError_t dropout_fwd(const void* a, long long lda, void* d, long long ldd, const int* state,
                        int is_bf16, int rows, int H, unsigned T, float scale, int layer, int rank,
                        hipStream_t s) {
   int vec = 0;
-  const hipError_t e = drop_check(is_bf16, a, lda, d, ldd, state, rows, H, scale, layer, rank, &vec);
+  const hipError_t e = row_check(is_bf16, a, lda, d, ldd, state, rows, H,
+                                 drop_args_ok(rows, H, scale, layer, rank), &vec);
   if (e != hipSuccess || rows == 0) return e;
-  return drop_pick_vec<false, ACT_NONE>(vec, a, lda, a, lda, d, ldd, state, rows, H, T, scale,
-                                        layer, rank, s);
+  return row_pick_vec(vec, [&](auto t, auto v) {
+    return drop_launch<decltype(t), decltype(v)::value, false, ACT_NONE>(
+        a, lda, a, lda, d, ldd, state, rows, H, T, scale, layer, rank, s);
+  });
 }
 
 hipError_t dropout_bwd(void* dd, long long ldd, const void* a, long long lda, const int* state,
                        int is_bf16, int rows, int H, unsigned T, float scale, int act, int layer,
                        int rank, hipStream_t s) {
   int vec = 0;
-  if (act != ACT_NONE && act != ACT_RELU && act != ACT_TANH) return hipErrorInvalidValue;
-  const hipError_t e = drop_check(is_bf16, dd, ldd, a, lda, state, rows, H, scale, layer, rank, &vec);
+  const hipError_t e = row_check(is_bf16, dd, ldd, a, lda, state, rows, H,
+                                 act_known(act) && drop_args_ok(rows, H, scale, layer, rank), &vec);
   if (e != hipSuccess || rows == 0) return e;
-  const void* x = dd;
-  if (act == ACT_RELU)
-    return drop_pick_vec<true, ACT_RELU>(vec, x, ldd, a, lda, dd, ldd, state, rows, H, T, scale,
-                                         layer, rank, s);
-  if (act == ACT_TANH)
-    return drop_pick_vec<true, ACT_TANH>(vec, x, ldd, a, lda, dd, ldd, state, rows, H, T, scale,
-                                         layer, rank, s);
-  return drop_pick_vec<true, ACT_NONE>(vec, x, ldd, a, lda, dd, ldd, state, rows, H, T, scale,
-                                       layer, rank, s);
+  return row_pick_act(act, [&](auto ac) {
+    return row_pick_vec(vec, [&](auto t, auto v) {
+      return drop_launch<decltype(t), decltype(v)::value, true, decltype(ac)::value>(
+          dd, ldd, a, lda, dd, ldd, state, rows, H, T, scale, layer, rank, s);
+    });
+  });
 }
 
 hipError_t dropout_tick(int* state, hipStream_t s) {

@@ -10,8 +10,8 @@
 // place, recomputing x from the saved z and the stored statistics with the forward's expression
 // (norm_x), so both directions see the same x bit for bit.
 //
-// Work split.  A row is cut into CHUNKS of 16 bytes (8 bf16 / 4 fp32; 1 fp32 in the scalar-load
-// form that takes fp32 rows of any width and alignment); C = H / chunk is what selects the form:
+// Work split.  A row is cut into the chunks of rowwise.h (8 bf16 / 4 fp32, or 1 fp32 in the
+// scalar-load form); C = H / chunk is what selects the form:
 //   wave form  (C <= 256: bf16 H <= 2048, fp32 H <= 1024, scalar H <= 256).  Every lane holds
 //     NORM_INFLIGHT = 4 chunks, all loaded before the first is used.  C <= 64: one chunk per row
 //     and lane, a row owned by the 2^lg >= C adjacent lanes of a wave (64 >> lg rows side by side)
@@ -25,9 +25,7 @@
 // over the row's lanes (then the wave-order LDS sum): no atomics, and the lanes that share a row
 // depend on H alone, so the result does not depend on the row count or the grid.  The backward's
 // two sums (dn, dn * x) of all rows in flight go through ONE butterfly.
-#include <type_traits>
-
-#include "common.h"
+#include "rowwise.h"
 
 namespace nnmpi {
 namespace {
@@ -35,19 +33,6 @@ namespace {
 constexpr int NORM_THREADS = 256;
 constexpr int NORM_WAVES = NORM_THREADS / WAVE;
 constexpr int NORM_INFLIGHT = 4;   // chunks per lane of the wave form
-constexpr int NORM_MAX_H = 8192;
-
-template <typename T, int VEC> struct RowVec;
-template <> struct RowVec<bf16, 8> { typedef bf16x8 type; };
-template <> struct RowVec<float, 4> { typedef f32x4 type; };
-template <> struct RowVec<float, 1> { typedef float type; };
-
-__device__ __forceinline__ float elem(const bf16x8& v, int i) { return (float)v[i]; }
-__device__ __forceinline__ float elem(const f32x4& v, int i) { return v[i]; }
-__device__ __forceinline__ float elem(const float& v, int) { return v; }
-__device__ __forceinline__ void put(bf16x8& v, int i, float x) { v[i] = (bf16)x; }
-__device__ __forceinline__ void put(f32x4& v, int i, float x) { v[i] = x; }
-__device__ __forceinline__ void put(float& v, int, float x) { v = x; }
 
 // Which rows and chunks a thread holds.  Wave form: U row groups in flight, a row on 2^lg lanes;
 // block form: the block's row, chunks NORM_THREADS apart.
@@ -284,8 +269,6 @@ bool norm_plan(int rows, int H, int vec, NormPlan& p) {
   return per <= p.nc;
 }
 
-template <int I> using IC = std::integral_constant<int, I>;
-
 // f(IC<NC>, bool_constant<BLOCK>) for the plan's form; only the forms a (T, VEC) pair can reach
 // are instantiated (bf16 stops at 4 chunks per thread, only the scalar form reaches 32)
 template <typename T, int VEC, typename F>
@@ -315,73 +298,23 @@ hipError_t norm_pick_kind(int norm, F&& f) {
   return hipErrorInvalidValue;
 }
 
+// The front both launchers share: the operand check (rowwise.h; ``op_ok``: the caller's own
+// arguments), the plan, and f(T(), IC<VEC>, IC<NC>, bool_constant<BLOCK>, IC<NORM>, plan) for
+// what they select.  No rows: success, nothing launched.
 template <typename F>
-hipError_t norm_pick_act(int act, F&& f) {
-  if (act == ACT_NONE) return f(IC<ACT_NONE>{});
-  if (act == ACT_RELU) return f(IC<ACT_RELU>{});
-  if (act == ACT_TANH) return f(IC<ACT_TANH>{});
-  return hipErrorInvalidValue;
-}
-
-bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
-// Elements per chunk for these operands (two row-strided matrices): 8 (bf16), 4 / 1 (fp32);
-// 0: not taken (bf16 rows that are not H % 8 == 0, 16-byte aligned with strides % 8 == 0)
-int norm_vec(int is_bf16, int H, const void* p0, long long ld0, const void* p1, long long ld1) {
-  const int v = is_bf16 ? 8 : 4;
-  const bool ok = H % v == 0 && ld0 % v == 0 && ld1 % v == 0 && aligned16(p0) && aligned16(p1);
-  return ok ? v : (is_bf16 ? 0 : 1);
-}
-
-bool overlap(const void* p0, long long ld0, const void* p1, long long ld1, int rows, int H, int es) {
-  const char* a = static_cast<const char*>(p0);
-  const char* b = static_cast<const char*>(p1);
-  const long long na = ((rows - 1) * ld0 + H) * es, nb = ((rows - 1) * ld1 + H) * es;
-  return a < b + nb && b < a + na;
-}
-
-template <typename T, int VEC>
-hipError_t fwd_launch(const NormPlan& p, const void* z, long long ldz, void* a, long long lda,
-                      float* stats, int rows, int H, int norm, int act, float eps, hipStream_t s) {
-  return norm_pick_form<T, VEC>(p, [&](auto nc, auto blk) {
-    return norm_pick_kind(norm, [&](auto kind) {
-      return norm_pick_act(act, [&](auto ac) {
-        norm_act_fwd_kernel<T, VEC, decltype(nc)::value, decltype(blk)::value,
-                            decltype(kind)::value, decltype(ac)::value>
-            <<<dim3(p.grid), dim3(NORM_THREADS), 0, s>>>(static_cast<const T*>(z), ldz,
-                                                         static_cast<T*>(a), lda, stats, rows, H,
-                                                         p.lg, eps);
-        return hipGetLastError();
-      });
+hipError_t norm_launch(int is_bf16, const void* p0, long long ld0, const void* p1, long long ld1,
+                       const float* stats, int rows, int H, int norm, bool op_ok, F&& f) {
+  int vec = 0;
+  NormPlan p;
+  op_ok = op_ok && (norm == NORM_LAYER || norm == NORM_RMS);
+  const hipError_t e = row_check(is_bf16, p0, ld0, p1, ld1, stats, rows, H, op_ok, &vec);
+  if (e != hipSuccess || rows == 0) return e;
+  if (!norm_plan(rows, H, vec, p)) return hipErrorInvalidValue;
+  return row_pick_vec(vec, [&](auto t, auto v) {
+    return norm_pick_form<decltype(t), decltype(v)::value>(p, [&](auto nc, auto blk) {
+      return norm_pick_kind(norm, [&](auto kind) { return f(t, v, nc, blk, kind, p); });
     });
   });
-}
-
-template <typename T, int VEC>
-hipError_t bwd_launch(const NormPlan& p, void* dn, long long ldd, const void* z, long long ldz,
-                      const float* stats, int rows, int H, int norm, hipStream_t s) {
-  return norm_pick_form<T, VEC>(p, [&](auto nc, auto blk) {
-    return norm_pick_kind(norm, [&](auto kind) {
-      norm_bwd_kernel<T, VEC, decltype(nc)::value, decltype(blk)::value, decltype(kind)::value>
-          <<<dim3(p.grid), dim3(NORM_THREADS), 0, s>>>(static_cast<T*>(dn), ldd,
-                                                       static_cast<const T*>(z), ldz, stats, rows,
-                                                       H, p.lg);
-      return hipGetLastError();
-    });
-  });
-}
-
-// the checks both launchers share; *vec = the chunk width to run (0 rows: nothing to launch)
-hipError_t norm_check(int is_bf16, const void* p0, long long ld0, const void* p1, long long ld1,
-                      const float* stats, int rows, int H, int norm, int* vec, NormPlan* plan) {
-  if (rows < 0 || H <= 0 || H > NORM_MAX_H || ld0 < H || ld1 < H) return hipErrorInvalidValue;
-  if (norm != NORM_LAYER && norm != NORM_RMS) return hipErrorInvalidValue;
-  if (rows == 0) return hipSuccess;
-  if (!p0 || !p1 || !stats) return hipErrorInvalidValue;
-  if (overlap(p0, ld0, p1, ld1, rows, H, is_bf16 ? 2 : 4)) return hipErrorInvalidValue;
-  *vec = norm_vec(is_bf16, H, p0, ld0, p1, ld1);
-  if (*vec == 0 || !norm_plan(rows, H, *vec, *plan)) return hipErrorInvalidValue;
-  return hipSuccess;
 }
 
 }  // namespace
@@ -389,26 +322,33 @@ hipError_t norm_check(int is_bf16, const void* p0, long long ld0, const void* p1
 hipError_t norm_act_fwd(const void* z, long long ldz, void* a, long long lda, float* stats,
                         int is_bf16, int rows, int H, int norm, int act, float eps,
                         hipStream_t s) {
-  int vec = 0;
-  NormPlan p;
-  if (act != ACT_NONE && act != ACT_RELU && act != ACT_TANH) return hipErrorInvalidValue;
-  if (!(eps >= 0.f)) return hipErrorInvalidValue;
-  const hipError_t e = norm_check(is_bf16, z, ldz, a, lda, stats, rows, H, norm, &vec, &p);
-  if (e != hipSuccess || rows == 0) return e;
-  if (vec == 8) return fwd_launch<bf16, 8>(p, z, ldz, a, lda, stats, rows, H, norm, act, eps, s);
-  if (vec == 4) return fwd_launch<float, 4>(p, z, ldz, a, lda, stats, rows, H, norm, act, eps, s);
-  return fwd_launch<float, 1>(p, z, ldz, a, lda, stats, rows, H, norm, act, eps, s);
+  const bool op_ok = act_known(act) && eps >= 0.f;   // (NaN: refused)
+  return norm_launch(is_bf16, z, ldz, a, lda, stats, rows, H, norm, op_ok,
+                     [&](auto t, auto v, auto nc, auto blk, auto kind, const NormPlan& p) {
+    typedef decltype(t) T;
+    return row_pick_act(act, [&](auto ac) {
+      norm_act_fwd_kernel<T, decltype(v)::value, decltype(nc)::value, decltype(blk)::value,
+                          decltype(kind)::value, decltype(ac)::value>
+          <<<dim3(p.grid), dim3(NORM_THREADS), 0, s>>>(static_cast<const T*>(z), ldz,
+                                                       static_cast<T*>(a), lda, stats, rows, H,
+                                                       p.lg, eps);
+      return hipGetLastError();
+    });
+  });
 }
 
 hipError_t norm_bwd(void* dn, long long ldd, const void* z, long long ldz, const float* stats,
                     int is_bf16, int rows, int H, int norm, hipStream_t s) {
-  int vec = 0;
-  NormPlan p;
-  const hipError_t e = norm_check(is_bf16, dn, ldd, z, ldz, stats, rows, H, norm, &vec, &p);
-  if (e != hipSuccess || rows == 0) return e;
-  if (vec == 8) return bwd_launch<bf16, 8>(p, dn, ldd, z, ldz, stats, rows, H, norm, s);
-  if (vec == 4) return bwd_launch<float, 4>(p, dn, ldd, z, ldz, stats, rows, H, norm, s);
-  return bwd_launch<float, 1>(p, dn, ldd, z, ldz, stats, rows, H, norm, s);
+  return norm_launch(is_bf16, dn, ldd, z, ldz, stats, rows, H, norm, true,
+                     [&](auto t, auto v, auto nc, auto blk, auto kind, const NormPlan& p) {
+    typedef decltype(t) T;
+    norm_bwd_kernel<T, decltype(v)::value, decltype(nc)::value, decltype(blk)::value,
+                    decltype(kind)::value>
+        <<<dim3(p.grid), dim3(NORM_THREADS), 0, s>>>(static_cast<T*>(dn), ldd,
+                                                     static_cast<const T*>(z), ldz, stats, rows, H,
+                                                     p.lg);
+    return hipGetLastError();
+  });
 }
 
 }  // namespace nnmpi

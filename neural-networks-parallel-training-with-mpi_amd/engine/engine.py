@@ -4,10 +4,8 @@ One step (per rank), replacing the reference's hot loop ``ref.py:155-211`` (Data
 ``.float()`` -> forward -> MSELoss -> autograd backward -> gather/average/send -> SGD):
 
     forward   h_i = act(h_{i-1} W_i^T + b_i)                  hidden layers (GEMM + epilogue)
-              (--norm layer | rms: z_i = h_{i-1} W_i^T + b_i, h_i = act(norm(z_i)) -- norm.hip;
-              its backward rewrites dZ_i in place right after the head / dgrad produced it)
-              (--dropout p: the next layer reads mask_i * h_i / (1 - p) -- dropout.hip; the
-              head / dgrad then run without act', dropout_bwd applies mask, scale and act')
+              (--norm / --dropout: the row-wise transforms behind the GEMM, their buffers and
+              their backward on dZ_i right after the head / dgrad produced it -- hidden.py)
     head      logits, loss, dlogits, dZ_{L-2}, dW_{L-1}, db   fused output layer + loss
               -> grad bucket(s) of layer L-1 ready -> all-reduce starts on the comm stream
     backward  for i = L-2 .. 0:
@@ -28,7 +26,7 @@ on the CPU (gloo) — that is the reference-semantics path and the test oracle.
 
 Layout: :meth:`MLPEngine._schedule` alone decides which ``_step_*`` body a batch runs; the
 comm-overlapped bodies share :class:`~.pipeline.BucketPipeline`; :class:`WeightImages` holds the
-row-band weight images.
+row-band weight images; :class:`~.hidden.HiddenChain` owns the hidden layers' norm and dropout.
 """
 from __future__ import annotations
 
@@ -39,9 +37,9 @@ import torch
 from ..utils.knobs import knob
 
 from ..models.mlp import MLPSpec
-from ..ops.torch_ops import dropout_state
 from ..parallel.sync import NativeRcclSync, NoSync, TorchDistSync
 from .arena import Arena
+from .hidden import HiddenChain
 from .optimizer import adam_hparams, make_optimizer, sgd_hparams
 from .pipeline import BucketPipeline
 
@@ -111,17 +109,12 @@ class MLPEngine:
         L = self.L = spec.n_layers
         w = spec.widths
         self.act, self.loss_kind = spec.activation, spec.loss
-        # hidden layers act(norm(z)) (norm.hip): no fused, grouped, row-band or one-launch tiny
-        # body takes a norm yet -- such a model runs the sequential body for every batch size
-        # (fp32 models of tiny widths on the fp32 GEMMs, as predict() does)
-        self.norm = None if spec.norm == "none" else spec.norm
-        if self.norm is not None:
-            use_tiny = overlap = False
-        # dropout of every hidden layer's activations (dropout.hip), in the same position: the
-        # sequential body only
-        self.p_drop = float(spec.dropout)
-        self._drop_seed, self._drop_rank = int(dropout_seed) & (2 ** 64 - 1), int(dropout_rank)
-        if self.p_drop != 0.0:
+        # the hidden layers' norm and dropout (engine/hidden.py).  No fused, grouped, row-band or
+        # one-launch tiny body takes either yet -- such a model runs the sequential body for
+        # every batch size (fp32 models of tiny widths on the fp32 GEMMs, as predict() does)
+        self.hidden = HiddenChain(spec, ops, self.R, dtype, self.device, dropout_seed,
+                                  dropout_rank)
+        if self.hidden.active:
             use_tiny = overlap = False
         bf16 = dtype == torch.bfloat16
         if use_tiny is None:
@@ -143,16 +136,6 @@ class MLPEngine:
         self.labels = None if mse else torch.zeros(R, dtype=torch.int64, device=dev)
         self.acts = [torch.zeros(R, w[i + 1], dtype=dtype, device=dev) for i in range(L - 1)]
         self.dzl = [torch.zeros(R, w[i + 1], dtype=dtype, device=dev) for i in range(L - 1)]
-        # with a norm: every hidden layer's pre-activations (the backward recomputes the
-        # normalised row from them) and per-row (mu, rstd) -- allocated once, like the rest
-        nh = L - 1 if self.norm is not None else 0
-        self.zpre = [torch.zeros(R, w[i + 1], dtype=dtype, device=dev) for i in range(nh)]
-        self.nstats = [torch.zeros(R, 2, dtype=torch.float32, device=dev) for i in range(nh)]
-        # with dropout: every hidden layer's dropped activations (acts keeps the undropped ones:
-        # the backward applies act' through them) and the generator's device state (seed, pass)
-        self.drop = [torch.zeros(R, w[i + 1], dtype=dtype, device=dev)
-                     for i in range(L - 1 if self.p_drop else 0)]
-        self.dstate = dropout_state(self._drop_seed, 0, dev) if self.p_drop else None
         self.dlogits = torch.zeros(R, w[-1], dtype=torch.float32, device=dev)
         self.loss_out = torch.zeros(4, dtype=torch.float32, device=dev)
         adam = optimizer != "sgd"
@@ -261,6 +244,7 @@ class MLPEngine:
     _rb_buf = property(lambda self: self.images.buf)
     _defer_plan = property(lambda self: self.pipe.defer_plan)
     _rb_pack = property(lambda self: self.images.pack)
+    drop = property(lambda self: self.hidden.drop)   # dropped activations; [] without dropout
 
     def _mark(self, name: str = "comm"):
         # (the default is the mark the pipeline's join() places: pipe.join(self._mark))
@@ -279,10 +263,6 @@ class MLPEngine:
     # ------------------------------------------------------------------------------------
     def _validate(self):
         w = self.spec.widths
-        if not 0.0 <= self.p_drop < 1.0:     # (also NaN)
-            raise ValueError(f"dropout must be in [0, 1), got {self.spec.dropout!r}")
-        if self.p_drop and (self.L - 1 > 256 or not 0 <= self._drop_rank < 2 ** 24):
-            raise ValueError("dropout: at most 256 hidden layers and ranks below 2^24")
         # (any output layer: heads beyond the skinny kernels run on the general path)
         if self.is_cuda and not self.use_tiny and self.dtype == torch.bfloat16:
             if any(w[i] % 8 or w[i + 1] % 8 for i in range(self.L - 1)):
@@ -383,85 +363,51 @@ class MLPEngine:
                               self.loss_out, self.ws, sgd=fz, loss_scale=self.loss_scale)
             for i in reversed(range(L)):
                 self.sync.ready(i)
-            self._drop_tick()       # an empty batch is a pass too: the ranks stay in step
+            self.hidden.tick()      # an empty batch is a pass too: the ranks stay in step
             return
+        hid = self.hidden
         x = self.X[:rows]
         h = self._forward(x, train=True)
         self._mark("fwd")
         last = L - 1
         dz = self._dzl(last - 1, rows) if L > 1 else None
         self._head(h, dz)
-        self._drop_bwd(last - 1)
-        self._norm_bwd(last - 1)
+        hid.backward(last - 1, dz, self.acts, rows)
         self._mark("head")
         self.sync.ready(last)
-        # what the layers read: with dropout the dropped activations, and act' is then applied
-        # by dropout_bwd (through the undropped ones), not by the head / dgrad epilogue
-        hid = self.drop if self.p_drop else self.acts
-        act = "none" if self.p_drop else self.act
         for i in range(L - 2, -1, -1):
-            x_in = hid[i - 1][:rows] if i > 0 else x
+            x_in = hid.reads(i - 1, self.acts, rows) if i > 0 else x
             for _ in self._wgrad_chunks(i, dz, x_in):
                 pass
             self.sync.ready(i)
             if i > 0:
                 dz_next = self._dzl(i - 1, rows)
-                ops.linear_dgrad(dz, ar.compute_weight(i), self.acts[i - 1][:rows], act, dz_next)
-                self._drop_bwd(i - 1)
-                self._norm_bwd(i - 1)
+                ops.linear_dgrad(dz, ar.compute_weight(i), self.acts[i - 1][:rows],
+                                 hid.epilogue_act, dz_next)
+                hid.backward(i - 1, dz_next, self.acts, rows)
                 dz = dz_next
         self._mark("bwd")
-        self._drop_tick()
-
-    def _drop_bwd(self, layer: int):
-        """With dropout, the head and linear_dgrad (run with "none") leave dL/d(dropped
-        activations) in the layer's dZ buffer: mask, scale and act' in place, the mask
-        regenerated from the pass number the forward used."""
-        if self.p_drop and layer >= 0:
-            rows = self.rows
-            self.ops.dropout_bwd(self._dzl(layer, rows), self.acts[layer][:rows], self.dstate,
-                                 self.p_drop, self.act, layer, self._drop_rank)
-
-    def _drop_tick(self):
-        """The last dropout launch of every training pass: the next one draws another mask."""
-        if self.p_drop:
-            self.ops.dropout_tick(self.dstate)
+        hid.tick()
 
     @property
     def dropout_step(self) -> int:
         """Training passes (forward_backward calls, empty and micro-batches included) since
-        construction: the pass number of the next mask, read from the device (host sync).
-        Assigning it (a resume) sets the device counter."""
-        if not self.p_drop:
-            return 0
-        self.synchronize(check=False)
-        return int(self.dstate[2].item())
+        construction: the pass number of the next mask, read from the device (host sync of the
+        engine's stream).  Assigning it (a resume) sets the device counter."""
+        with self._on_stream():
+            return self.hidden.get_step()
 
     @dropout_step.setter
     def dropout_step(self, n: int):
-        if self.p_drop:
-            with self._on_stream(), torch.no_grad():
-                self.dstate[2:3].fill_(int(n))
+        with self._on_stream(), torch.no_grad():
+            self.hidden.set_step(n)
 
-    @property
-    def dropout_seed(self) -> int:
-        return self._drop_seed
+    dropout_seed = property(lambda self: self.hidden.seed)
 
     @dropout_seed.setter
     def dropout_seed(self, seed: int):
-        self._drop_seed = int(seed) & (2 ** 64 - 1)
-        if self.p_drop:
-            with self._on_stream(), torch.no_grad():
-                self.dstate[:2].copy_(dropout_state(self._drop_seed, 0, "cpu")[:2])
-
-    def _norm_bwd(self, layer: int):
-        """With a norm, the head and linear_dgrad leave dL/d(normalised row) in the layer's dZ
-        buffer (they apply act' through the saved activations): turn it into dL/dz in place,
-        before the layer's weight gradient and the next dgrad read it."""
-        if self.norm is not None and layer >= 0:
-            rows = self.rows
-            self.ops.norm_bwd(self._dzl(layer, rows), self.zpre[layer][:rows],
-                              self.nstats[layer][:rows], self.norm)
+        with self._on_stream(), torch.no_grad():
+            self.hidden.set_seed(seed)
 
     def _wgrad_chunks(self, i: int, dz, x_in, bf16_out: bool = False):
         """Weight gradient of layer i; a layer cut into output-row chunk buckets (Arena
@@ -501,27 +447,16 @@ class MLPEngine:
     def _forward(self, x, train: bool = False):
         """The hidden layers; ``train``: with dropout (the forward-only paths run without it and
         do not advance the pass number)."""
-        h = x
+        h, rows, ar = x, self.rows, self.arena
         for i in range(self.L - 1):
-            out = self.acts[i][:self.rows]
-            W, b = self.arena.compute_weight(i), self.arena.bias(i)
-            if self.norm is None:
-                self.ops.linear_act(h, W, b, self.act, out)
-            else:
-                z = self.zpre[i][:self.rows]
-                self.ops.linear_act(h, W, b, "none", z)
-                self.ops.norm_act(z, self.norm, self.act, out, self.nstats[i][:self.rows])
-            h = out
-            if train and self.p_drop:
-                h = self.drop[i][:self.rows]
-                self.ops.dropout(out, h, self.dstate, self.p_drop, i, self._drop_rank)
+            h = self.hidden.forward(i, h, ar.compute_weight(i), ar.bias(i), self.acts[i][:rows],
+                                    rows, train)
         return h
 
     def _head(self, h, dz, sgd=None):
         rows, ar, last = self.rows, self.arena, self.L - 1
         kw = {"sgd": sgd} if sgd is not None else {}
-        # (with dropout h is the dropped activation: dropout_bwd applies act', see _drop_bwd)
-        act_prev = self.act if self.L > 1 and not self.p_drop else "none"
+        act_prev = self.hidden.epilogue_act if self.L > 1 else "none"
         self.ops.head(h, ar.weight(last), ar.bias(last), *self._targets(rows),
                       self.loss_kind, self.inv_count, act_prev, dz,
                       ar.grad_weight(last), ar.grad_bias(last), self.dlogits[:rows], self.loss_out,

@@ -64,60 +64,56 @@ class HipOps(OpSet):
                                       a_prev.stride(0), _p(out), out.stride(0), M, N, K,
                                       ACT_CODES[act], self.stream)
 
-    # ---------------- layer / RMS normalisation (norm.hip) ----------------
+    # ---------------- row-chunk ops: norm.hip, dropout.hip (csrc/kernels/rowwise.h) ------------
     @staticmethod
-    def _norm_rows(what: str, norm: str, stats, *mats):
-        """(rows, H, is_bf16, row strides) of the row-strided operands of a norm launch."""
+    def _row_operands(what: str, *mats):
+        """(rows, H, is_bf16, row strides) of a row-chunk launch's operands (one row: >= H)."""
         rows, H = mats[0].shape
-        _check(norm in NORM_CODES, f"{what}: norm layer | rms, got {norm!r}")
         _check(all(t.dim() == 2 and tuple(t.shape) == (rows, H) and t.dtype == mats[0].dtype and
                    (t.stride(1) == 1 or H == 1) for t in mats) and
                mats[0].dtype in (torch.bfloat16, torch.float32),
                f"{what}: bf16 / fp32 [rows, H] operands of one dtype, unit column stride")
-        _check(stats.dtype == torch.float32 and stats.is_contiguous() and
-               tuple(stats.shape) == (rows, 2), f"{what}: dense fp32 statistics [rows, 2]")
         lds = [t.stride(0) if rows > 1 else max(t.stride(0), H) for t in mats]
         return rows, H, 1 if mats[0].dtype == torch.bfloat16 else 0, lds
+
+    def _check_norm(self, what: str, norm: str, stats, rows: int):
+        _check(norm in NORM_CODES, f"{what}: norm layer | rms, got {norm!r}")
+        _check(stats.dtype == torch.float32 and stats.is_contiguous() and
+               tuple(stats.shape) == (rows, 2), f"{what}: dense fp32 statistics [rows, 2]")
 
     def norm_act(self, z, norm: str, act: str, out, stats, eps: float = NORM_EPS):
         """See OpSet.norm_act.  One launch; what the kernel does not take (bf16 rows that are
         not H % 8 == 0 and 16-byte aligned, H > 8192, ``out`` overlapping ``z``) raises before
         anything is launched."""
-        rows, H, bf, (ldz, lda) = self._norm_rows("norm_act", norm, stats, z, out)
+        rows, H, bf, (ldz, lda) = self._row_operands("norm_act", z, out)
+        self._check_norm("norm_act", norm, stats, rows)
         self.lib.norm_act_fwd(_p(z), ldz, _p(out), lda, _p(stats), bf, rows, H, NORM_CODES[norm],
                               ACT_CODES[act], float(eps), self.stream)
 
     def norm_bwd(self, dn, z, stats, norm: str):
-        rows, H, bf, (ldd, ldz) = self._norm_rows("norm_bwd", norm, stats, dn, z)
+        rows, H, bf, (ldd, ldz) = self._row_operands("norm_bwd", dn, z)
+        self._check_norm("norm_bwd", norm, stats, rows)
         self.lib.norm_bwd(_p(dn), ldd, _p(z), ldz, _p(stats), bf, rows, H, NORM_CODES[norm],
                           self.stream)
 
-    # ---------------- dropout (dropout.hip) ----------------
-    @staticmethod
-    def _drop_rows(what: str, state, layer: int, rank: int, *mats):
-        """(rows, H, is_bf16, row strides) of the row-strided operands of a dropout launch."""
-        rows, H = mats[0].shape
-        _check(all(t.dim() == 2 and tuple(t.shape) == (rows, H) and t.dtype == mats[0].dtype and
-                   (t.stride(1) == 1 or H == 1) for t in mats) and
-               mats[0].dtype in (torch.bfloat16, torch.float32),
-               f"{what}: bf16 / fp32 [rows, H] operands of one dtype, unit column stride")
+    def _check_drop(self, what: str, state, layer: int, rank: int, device):
         _check(state.dtype == torch.int32 and state.is_contiguous() and state.numel() == 4 and
-               state.device == mats[0].device, f"{what}: int32[4] state on the operands' device")
+               state.device == device, f"{what}: int32[4] state on the operands' device")
         _check(0 <= layer < 256 and 0 <= rank < 2 ** 24, f"{what}: layer < 256, rank < 2^24")
-        lds = [t.stride(0) if rows > 1 else max(t.stride(0), H) for t in mats]
-        return rows, H, 1 if mats[0].dtype == torch.bfloat16 else 0, lds
 
     def dropout(self, a, out, state, p: float, layer: int, rank: int):
         """See OpSet.dropout.  One launch; what the kernel does not take (bf16 rows that are not
         H % 8 == 0 and 16-byte aligned, H > 8192, ``out`` overlapping ``a``) raises before
         anything is launched."""
-        rows, H, bf, (lda, ldd) = self._drop_rows("dropout", state, layer, rank, a, out)
+        rows, H, bf, (lda, ldd) = self._row_operands("dropout", a, out)
+        self._check_drop("dropout", state, layer, rank, a.device)
         T, scale = dropout_consts(p)
         self.lib.dropout_fwd(_p(a), lda, _p(out), ldd, _p(state), bf, rows, H, T, scale, layer,
                              rank, self.stream)
 
     def dropout_bwd(self, dd, a, state, p: float, act: str, layer: int, rank: int):
-        rows, H, bf, (ldd, lda) = self._drop_rows("dropout_bwd", state, layer, rank, dd, a)
+        rows, H, bf, (ldd, lda) = self._row_operands("dropout_bwd", dd, a)
+        self._check_drop("dropout_bwd", state, layer, rank, dd.device)
         T, scale = dropout_consts(p)
         self.lib.dropout_bwd(_p(dd), ldd, _p(a), lda, _p(state), bf, rows, H, T, scale,
                              ACT_CODES[act], layer, rank, self.stream)
